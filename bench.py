@@ -2,8 +2,12 @@
 """Benchmark of the MI355X rdc allreduce path (BASELINE.json metric:
 "allreduce GB/s (device-resident fp32) at 1/2/4/8 GPUs; % xGMI roofline").
 
-    python bench.py --gpus N --steps K --warmup W
-    (N>1 under a launcher: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...;
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    (a plain run sets up, warms up, times the K steps and prints the line;
+     --full adds the CPU baselines, the oracle checks and, at N>1, the untuned
+     timing, link probe, role timeline, ring schedule, other configs and RCCL;
+     --dump-outputs writes the last timed step's result to DIR/<name>.npy;
+     N>1 under a launcher: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...;
      N>1 without one, WORLD_SIZE unset: bench.py starts that launcher itself as a child process)
 
 Workload: a 1 GiB fp32 buffer per GPU (the cfg3 buffer), synthetic data
@@ -66,7 +70,51 @@ def parse():
     ap.add_argument("--autotune-reps", type=int, default=3,
                     help="N>1: before the warm-up, RdcCommAutotune times the launch shapes (role split, grid, "
                          "tile) for this buffer size on this node and keeps the fastest (0 = library defaults)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baselines, the oracle checks, "
+                         "and at N>1 the untuned timing, link probe, role timeline, ring schedule, other configs "
+                         "and the RCCL comparison (a plain run sets up, warms up, times the steps and prints)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step left in the caller's buffer to "
+                         "DIR/<name>.npy (float32, float64 for float64 runs; a fixed seeded sample of a large buffer)")
     return ap.parse_args()
+
+
+DUMP_MAX_ELEMS = 4 << 20      # 16 MiB of float32 (32 MiB of float64) per dumped array
+DUMP_SEED = 0x5EEDD0B5
+
+
+def sample_outputs(torch, tensors):
+    """The caller-visible result of the last timed step as one host array
+    (float32; float64 stays float64): `tensors` is the buffer, or the buckets
+    in order.  Up to DUMP_MAX_ELEMS elements it is the whole result; a larger
+    one is sampled at fixed positions (the first and last DUMP_MAX_ELEMS / 4
+    elements and DUMP_MAX_ELEMS / 2 seeded random positions in between, in
+    increasing order), the same positions in every run with the same
+    arguments.  Gathered on the device, so only the sample crosses PCIe."""
+    import numpy as np
+    sizes = [t.numel() for t in tensors]
+    n = sum(sizes)
+    odt = torch.float64 if tensors[0].dtype == torch.float64 else torch.float32
+    if n <= DUMP_MAX_ELEMS:
+        return torch.cat([t.reshape(-1) for t in tensors]).to(odt).cpu().numpy()
+    q = DUMP_MAX_ELEMS // 4
+    mid = np.sort(np.random.default_rng(DUMP_SEED).integers(q, n - q, size=2 * q, dtype=np.int64))
+    idx = np.concatenate([np.arange(q, dtype=np.int64), mid, np.arange(n - q, n, dtype=np.int64)])
+    ends = np.cumsum(sizes)
+    which = np.searchsorted(ends, idx, side="right")
+    parts = []
+    for b in np.unique(which):
+        local = idx[which == b] - (ends[b] - sizes[b])
+        parts.append(tensors[b].reshape(-1)[torch.from_numpy(local).to(tensors[b].device)].to(odt).cpu())
+    return torch.cat(parts).numpy()
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def load_traffic(kernel_key):
@@ -898,7 +946,7 @@ def main():
         dc = ctypes.c_uint64()
         check_call(_LIB.RdcCommGetParam(comm.handle, b"direct_check", ctypes.byref(dc)))
         direct_selfcheck = {0: "not run", 1: "passed", 2: "failed"}.get(int(dc.value), int(dc.value))
-    if world > 1 and args.autotune_reps > 0 and args.algo == "auto" and args.buckets == 1:
+    if args.full and world > 1 and args.autotune_reps > 0 and args.algo == "auto" and args.buckets == 1:
         # what a drop-in caller gets: the untuned default for this buffer,
         # timed (a few steps, max over ranks) before the autotune replaces it
         ms_u = timed_ms(step, comm, sp, dist, torch, max(3, min(args.steps, 10)), warm=1)
@@ -973,7 +1021,18 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         wall, kern_ms = float(tt[0]), float(tt[1])
 
-    # Everything after the timed region is informational.  A failure there
+    # what the last timed step left in the caller's buffer (every rank of an
+    # allreduce holds the same result: rank 0 writes), taken before any extra
+    # touches the buffer
+    if args.dump_outputs and rank == 0:
+        if world == 1:
+            dumped = {"reduce_dst": sample_outputs(torch, [dst])}
+        else:
+            dumped = {"allreduce_result": sample_outputs(torch, [buf] if max(1, args.buckets) == 1 else bks)}
+        write_outputs(args.dump_outputs, dumped)
+        del dumped
+
+    # Everything after the timed region is informational (--full).  A failure there
     # (e.g. a device wait timing out) must not cost the headline line: every
     # extra runs guarded; inside, every step agrees on failure over the CPU
     # process group (sync_check), so all ranks leave a failed extra together;
@@ -1014,10 +1073,11 @@ def main():
             return partial if partial else None
         return res
 
-    multi = world > 1 and args.buckets == 1 and args.algo == "auto"
+    full = args.full
+    multi = full and world > 1 and args.buckets == 1 and args.algo == "auto"
     f32 = args.dtype == "float32"
     roles = ring_cmp = extra = rccl = tcp = checks = None
-    if world > 1:
+    if full and world > 1:
         # the measured link rates (every rank idle), after the timed region so
         # that a failure here cannot cost the headline
         probe = guarded("xgmi_probe", lambda: xgmi_probe(_LIB, comm, sp, dist, torch), need_s=5)
@@ -1060,18 +1120,18 @@ def main():
         rccl = guarded("rccl_comparison", lambda: rccl_compare(S, world, rank, local, dist, torch, args.rccl_steps,
                                                                limit_s=min(150.0, budget.left() - 15)),
                        need_s=45)
-    if world > 1 and args.cpu_seconds > 0:
+    if full and world > 1 and args.cpu_seconds > 0:
         tcp = guarded("cpu_tcp_ring", lambda: cpu_tcp_ring(S, world, rank, dist), needs_comm=False, need_s=20)
 
     # spot check (outside the timed region): N=1 reduce result vs oracle on a slice
     check = None
-    if world == 1 and not args.no_check:
+    if full and world == 1 and not args.no_check:
         from oracle import oracle as O
         m = min(count, 1 << 16)
         d0 = O.fill(m, dt_enum, 0x5EED0000, 0)  # the generator is position-keyed: first m elements
         s0 = O.fill(m, dt_enum, 0x5EED0000, 1)
         acc = d0.copy()
-        for _ in range(args.warmup + args.steps):
+        for _ in range(max(1, args.warmup) + args.steps):  # the first checked step runs even with --warmup 0
             O.reducer(s0, acc, dt_enum, 2)
         got = dst[:m].cpu().view(torch.uint8).numpy()  # bytes (numpy has no bfloat16)
         check = bool(got.tobytes() == acc.tobytes())
@@ -1134,7 +1194,7 @@ def main():
                             "busbw = S / t x 2(n-1)/n (algbw_GBps = S / t)",
         "algbw_GBps": round(S / (wall / args.steps) / 1e9, 2),
         "roofline": roof,
-        "cpu_baseline": cpu_baseline(S, args.cpu_seconds) if world == 1 else None,
+        "cpu_baseline": cpu_baseline(S, args.cpu_seconds) if full and world == 1 else None,
     }
     if world > 1:
         out.update(multi_keys)
@@ -1170,7 +1230,8 @@ def main():
         out["oracle_check"] = check
     if extras_error:
         out["extras_error"] = extras_error
-    if world > 1:
+    out["full"] = full
+    if full and world > 1:
         out["extras_budget_s"] = args.extras_budget_s
         out["extras_wall_s"] = extras_wall
         out["extras_skipped"] = extras_skipped

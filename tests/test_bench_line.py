@@ -86,6 +86,33 @@ def test_a_missing_key_is_reported():
         "host_inclusive_1GiB.algbw_GBps_pcie_inclusive"}
 
 
+def test_dumped_outputs_are_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a result up to DUMP_MAX_ELEMS elements is written whole;
+    a larger one at fixed positions (head, seeded middle, tail, increasing),
+    the same whether the result is one buffer or buckets in order, and the
+    same from call to call; halves are written as float32, float64 as float64."""
+    import numpy as np
+    import torch
+    bench = load_bench()
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1024)
+    small = torch.arange(1000, dtype=torch.float32)
+    assert np.array_equal(bench.sample_outputs(torch, [small]), small.numpy())
+    n = 10007
+    big = torch.arange(n, dtype=torch.float32)
+    a = bench.sample_outputs(torch, [big])
+    assert a.dtype == np.float32 and a.shape == (1024,)
+    assert np.array_equal(a[:256], np.arange(256)) and np.array_equal(a[-256:], np.arange(n - 256, n))
+    assert np.all(np.diff(a) >= 0) and a[256] >= 256 and a[767] < n - 256   # values are their own positions
+    assert np.array_equal(bench.sample_outputs(torch, [big]), a)
+    buckets = list(torch.split(big, [5000, 1, 5006]))                       # ragged buckets, one of them tiny
+    assert np.array_equal(bench.sample_outputs(torch, buckets), a)
+    assert bench.sample_outputs(torch, [big.to(torch.float16)]).dtype == np.float32
+    assert bench.sample_outputs(torch, [big.to(torch.float64)]).dtype == np.float64
+    bench.write_outputs(str(tmp_path / "d"), {"x": a})
+    assert np.array_equal(np.load(str(tmp_path / "d" / "x.npy")), a)
+    assert 8 * load_bench().DUMP_MAX_ELEMS <= 64 << 20   # the one dumped array stays under 64 MB, float64 included
+
+
 def test_main_composes_the_line_with_compose_multi():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "roof, algo_name, multi_keys = compose_multi(_LIB, ctx)" in src

@@ -54,7 +54,7 @@ def test_bench_torchrun_two_ranks():
     port = free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--bytes", str(64 << 20), "--extra-steps", "2",
+           "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--bytes", str(64 << 20), "--extra-steps", "2",
            "--ring-steps", "2", "--cpu-seconds", "1"]
     p = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
@@ -100,7 +100,7 @@ def test_bench_self_launches_its_ranks():
     measures N ranks."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1",
            "--bytes", str(16 << 20), "--extra-steps", "0", "--rccl-steps", "0", "--cpu-seconds", "0",
            "--autotune-reps", "0"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
@@ -120,7 +120,7 @@ def test_bench_tiny_extras_budget():
     port = free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--bytes", str(16 << 20), "--extras-budget-s", "1",
+           "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--bytes", str(16 << 20), "--extras-budget-s", "1",
            "--autotune-reps", "0"]
     p = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
@@ -143,7 +143,7 @@ def test_bench_recovers_from_autotune_failure():
     port = free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "2", "--bytes", str(16 << 20), "--autotune-reps", "1",
+           "--gpus", "2", "--full", "--steps", "3", "--warmup", "2", "--bytes", str(16 << 20), "--autotune-reps", "1",
            "--extra-steps", "0", "--ring-steps", "0", "--rccl-steps", "0", "--cpu-seconds", "0"]
     # rank 1 skips autotune: rank 0's candidates wait for it until RDC_TIMEOUT,
     # so rank 0's channel really fails on the device
@@ -158,6 +158,73 @@ def test_bench_recovers_from_autotune_failure():
     assert out["config"]["launch"]["source"] == "library defaults (automatic rule)", out["config"]
     chk = out["oracle_check"]
     assert all(chk.get(k) is True for k in PARITY_KEYS), chk
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain N = 1 run (no --full) times the steps and prints the line
+    without the CPU baseline or the oracle spot check, and --dump-outputs
+    writes what the last timed step left in dst: here the whole 8 MiB buffer,
+    bit-exact against the oracle's dst += src applied once per executed step."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    from oracle import oracle as O
+    steps, warmup, nbytes = 3, 2, 8 << 20
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+           str(warmup), "--bytes", str(nbytes), "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["cpu_baseline"] is None and "oracle_check" not in out
+    assert out["steps"] == steps and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["value"] == pytest.approx(nbytes / (out["ms_per_step"] * 1e-3) / 1e9, rel=0.01)
+    assert sorted(os.listdir(str(tmp_path / "out"))) == ["reduce_dst.npy"]
+    got = np.load(str(tmp_path / "out" / "reduce_dst.npy"))
+    n = nbytes // 4
+    assert got.dtype == np.float32 and got.shape == (n,)
+    acc = O.fill(n, O.DT_FLOAT32, 0x5EED0000, 0)
+    src = O.fill(n, O.DT_FLOAT32, 0x5EED0000, 1)
+    for _ in range(warmup + steps):
+        O.reducer(src, acc, O.DT_FLOAT32, O.OP_SUM)
+    assert got.tobytes() == acc.tobytes()
+
+
+def test_bench_plain_two_ranks_dumps_the_allreduce_result(tmp_path):
+    """A plain N = 2 run (self-launched, no --full, library default shape)
+    carries none of the extras, and its dump is the buffer after every
+    in-place launch up to the last timed one: the first checked step, W - 1
+    more warm-up steps and K timed steps, each the oracle's ring order over
+    what the step before left on both ranks."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    from oracle import oracle as O
+    steps, warmup, nbytes = 2, 2, 4 << 20
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup",
+           str(warmup), "--bytes", str(nbytes), "--autotune-reps", "0", "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["n_gpus"] == 2 and out["steps"] == steps and out["ms_per_step"] > 0
+    for k in ("oracle_check", "extra_configs", "ring_schedule", "role_timeline", "rccl_comparison", "cpu_tcp_ring",
+              "extras_skipped", "autotune"):
+        assert k not in out, k
+    assert out["roofline"]["xgmi_probe"] is None and out["cfg3_schedule"]["untuned"]["ms_per_step"] is None
+    assert sorted(os.listdir(str(tmp_path / "out"))) == ["allreduce_result.npy"]
+    got = np.load(str(tmp_path / "out" / "allreduce_result.npy"))
+    n = nbytes // 4
+    assert got.dtype == np.float32 and got.shape == (n,)
+    xs = [O.fill(n, O.DT_FLOAT32, 0x5EED0000, r) for r in range(2)]
+    for _ in range(warmup + steps):
+        res = O.expected_allreduce(xs, O.DT_FLOAT32, O.OP_SUM)
+        xs = [res.copy(), res.copy()]
+    assert got.tobytes() == xs[0].tobytes()
 
 
 def test_launcher_cpp_known_answer(known_answer_exe):

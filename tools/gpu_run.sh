@@ -61,7 +61,7 @@ for step in "$@"; do
             || { tail -20 $OUT/smoke.txt; exit 1; }
         tail -1 $OUT/smoke.txt ;;
     bench1)
-        timeout -k 10 300 python3 bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err \
+        timeout -k 10 300 python3 bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err \
             || { tail -20 $OUT/bench_n1.err; exit 1; }
         cat $OUT/bench_n1.json
         rm -rf $OUT/prof_n1
@@ -72,7 +72,7 @@ for step in "$@"; do
         head -3 $OUT/bench_n1_kernel_stats.csv ;;
     benchN)
         tagged=$OUT/bench_n$a1$(echo "${a2:+_$a2}" | tr ',-' '__').txt   # one file per (n, args)
-        run_bench_n $a1 $tagged $(echo "$a2" | tr ',' ' ') || { tail -20 $tagged.err; exit 1; }
+        run_bench_n $a1 $tagged --full $(echo "$a2" | tr ',' ' ') || { tail -20 $tagged.err; exit 1; }
         [ "$tagged" = "$OUT/bench_n$a1.txt" ] || cp $tagged $OUT/bench_n$a1.txt
         grep '^{' $tagged | head -c 400; echo ;;
     pmc1)
@@ -96,7 +96,7 @@ for step in "$@"; do
             e=$([ $v = A ] && envset "$a2" || envset "$a3")
             port=$((port + 11))
             env $e timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                --master-addr 127.0.0.1 --master-port $port bench.py --gpus 2 --steps 30 --extra-steps 0 \
+                --master-addr 127.0.0.1 --master-port $port bench.py --gpus 2 --full --steps 30 --extra-steps 0 \
                 --rccl-steps 0 --cpu-seconds 0 --no-check --autotune-reps 0 --extras-budget-s 30 $extra \
                 > $OUT/ab_${a1}_$v.$port.txt 2>&1 || { tail -20 $OUT/ab_${a1}_$v.$port.txt; exit 1; }
             echo "$v $(grep '^{' $OUT/ab_${a1}_$v.$port.txt | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], (d.get("ring_schedule") or {}).get("ms_per_step"))')"
