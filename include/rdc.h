@@ -324,6 +324,15 @@ public:
     virtual void Allreduce(void* sendrecvbuf, uint64_t count, mpi::DataType dtype, mpi::OpType op) {
         detail::Check(RdcAllreduceOn(handle_, sendrecvbuf, count, (int)dtype, (int)op), "Allreduce");
     }
+    /*! \brief in-place reduce-scatter of count elements (host or device memory):
+     *  TryReduceScatterRing (communicator_base.h:217-233, "after the function,
+     *  node k get k-th segment of the reduction result"; communicator_collective.cc:
+     *  115-182).  Chunk GetRank() of utils::Split(0, count, n) receives the
+     *  reduction, with Allreduce's bits (the ring order at every size); every
+     *  other byte of sendrecvbuf stays as passed */
+    virtual void ReduceScatter(void* sendrecvbuf, uint64_t count, mpi::DataType dtype, mpi::OpType op) {
+        detail::Check(RdcReduceScatterOn(handle_, sendrecvbuf, count, (int)dtype, (int)op), "ReduceScatter");
+    }
     /*! \brief allreduce with a custom HOST reducer (communicator.h:92-93, virtual
      *  here).  sendrecvbuf needs an item size (Count()).  Ring order per Split
      *  chunk above rdc_reduce_ring_mincount bytes, the tree's order at or below
@@ -611,6 +620,23 @@ template <typename OP, typename DType>
 inline void Allreduce(DType* sendrecvbuf, uint64_t count, const std::string& comm_name = kMainCommName) {
     if (GetWorldSize() == 1 || count == 0) return;  // communicator_base.h:133-138
     GetCommunicator(comm_name)->Allreduce(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType);
+}
+
+/*! \brief in-place reduce-scatter (MI355X addition to the public surface: the
+ *  reference has it only as a schedule step, Communicator::TryReduceScatterRing,
+ *  communicator_collective.cc:115-182).  Returns this rank's element range
+ *  [first, second) of utils::Split(0, count, n): on return it holds the
+ *  reduction, with the bits Allreduce<OP, DType> puts there; every other
+ *  element of sendrecvbuf stays as passed */
+template <typename OP, typename DType>
+inline std::pair<uint64_t, uint64_t> ReduceScatter(DType* sendrecvbuf, uint64_t count,
+                                                   const std::string& comm_name = kMainCommName) {
+    if (GetWorldSize() == 1 || count == 0) return std::pair<uint64_t, uint64_t>(0, count);
+    comm::ICommunicator* c = GetCommunicator(comm_name);
+    c->ReduceScatter(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType);
+    uint64_t lo = 0, hi = 0;
+    detail::Check(RdcPlanSplit(count, c->GetWorldSize(), c->GetRank(), &lo, &hi), "ReduceScatter");
+    return std::pair<uint64_t, uint64_t>(lo, hi);
 }
 
 /*! \brief in-place allreduce of a typed Buffer (include/api.h:65-66; declared

@@ -85,6 +85,25 @@ int RdcBroadcastOn(void* comm, void* sendrecv, size_t size, int root);
 int RdcAllgather(void** bufs, const size_t* sizes);
 int RdcAllgatherOn(void* comm, void** bufs, const size_t* sizes);
 
+/* In-place reduce-scatter (Communicator::TryReduceScatterRing,
+ * src/comm/communicator_collective.cc:115-182; include/comm/communicator_base.h:
+ * 217-233: "after the function, node k get k-th segment of the reduction
+ * result"; the reference reaches it only as the first half of its ring
+ * allreduce).  Chunk c = utils::Split(0, count, n)[c] (RdcPlanSplit), the
+ * allreduce's chunk map.  On return chunk `rank` of sendrecv holds the
+ * reduction of that chunk over all ranks, bit-identical to chunk `rank` of
+ * what RdcAllreduce returns on the same inputs by the ring order,
+ * x[r] (+) (x[r+1] (+) ... (+) x[r-1]).  The ring order applies at EVERY size:
+ * TryReduceScatterRing has no tree branch, so rdc_reduce_ring_mincount does
+ * not apply.  Every byte of sendrecv outside chunk `rank` is left exactly as
+ * the caller passed it (the reference leaves ring partials there).  count = 0
+ * or world size 1 succeed without touching the GPU; with count < n some chunks
+ * are empty and their ranks still take part.  Host or device memory
+ * (detected); synchronous.  A host buffer goes up whole, and only chunk `rank`
+ * is copied back.  RdcReduceScatter uses the "main" communicator. */
+int RdcReduceScatter(void* sendrecv, size_t count, int dtype, int op);
+int RdcReduceScatterOn(void* comm, void* sendrecv, size_t count, int dtype, int op);
+
 /* Coalesced (bucketed) allreduce: the result of one RdcAllreduce per buffer,
  * in order, bit-identical, but the buffers move in fused launches (BASELINE
  * cfg5 / test/mallreduce.cc's back-to-back shape).  A list takes the schedule
@@ -184,6 +203,25 @@ int RdcCommAllreduce(void* comm, void* dev_buf, size_t count, int dtype, int op,
  * fold of TryReduceTree to rank 0, every rank receiving the root's bits) as one one-shot
  * style hand-off; algo 4 forces that tree order for any size. */
 int RdcCommAllreduceEx(void* comm, void* dev_buf, size_t count, int dtype, int op, int algo, void* stream);
+/* Device-resident in-place reduce-scatter (see RdcReduceScatter for the
+ * result; TryReduceScatterRing, communicator_collective.cc:115-182),
+ * stream-ordered; errors raised inside the kernels surface at RdcCommCheck.
+ * algo: 0 auto; 2 mesh, pushed (the scratch schedule: every rank pushes the
+ * other chunks to their owners, owner r folds chunk r into its own buffer;
+ * works in single-process groups and can be captured in a hipGraph; a launch
+ * ends only after every peer's launch ended, so the scratch slots need no gate
+ * in whatever launch follows); 6 direct (registered buffers, one process per
+ * rank: owner r folds chunk r straight out of the n buffers and stores it into
+ * its own only).  Auto takes direct exactly where RdcCommAllreduceEx's auto
+ * does (same channel check, the RdcPlanDirectAuto threshold — measured for the
+ * allreduce, provisional here —, never while capturing), else the mesh; a
+ * direct call that cannot run (a refused mapping, buffers that differ mod 16,
+ * a released channel) falls back to the mesh on every rank and is counted in
+ * "direct_fallback".  algo 1, 3, 4 and 5 are invalid arguments: the ring would
+ * clobber the other chunks, the one-shot and the tree make no sense for a
+ * scatter, and the pull mesh is dominated by direct wherever direct can run.
+ * RdcCommLastLaunch then reports algo 2 or 6 and 0 gather blocks. */
+int RdcCommReduceScatter(void* comm, void* dev_buf, size_t count, int dtype, int op, int algo, void* stream);
 /* device-resident coalesced allreduce (see RdcAllreduceCoalesced), stream-ordered.
  * The per-group unit table is cached by (buffers, counts): after a first
  * (warm-up) call with the same buckets, launches need no host->device copy
@@ -407,6 +445,23 @@ int RdcPlanDirectAuto(int n, size_t bytes, size_t scratch_bytes, size_t oneshot_
 int RdcPlanHbmBytes(int n, size_t count, int dtype, int algo, uint64_t* out5);
 int RdcPlanAllreduce(int n, size_t count, int dtype, size_t scratch_bytes, int algo, size_t tile_bytes,
                      int max_blocks, uint64_t* out, int max_pieces, int* out_pieces);
+
+/* utils::Split(0, count, n)[rank] (include/utils/utils.h:59-70) in 64-bit
+ * arithmetic: the element range [*begin, *end) of chunk `rank`, the chunk a
+ * reduce-scatter leaves on that rank and the allreduce's owner map. */
+int RdcPlanSplit(size_t count, int n, int rank, uint64_t* begin, uint64_t* end);
+/* The launches of a mesh reduce-scatter (RdcCommReduceScatter, algo 2), in
+ * RdcPlanAllreduce's records: the offsets, lengths, mis and tiles of
+ * RdcPlanAllreduce(algo 2) for the same arguments, nb_gather = 0, and the grid
+ * split between scatter and reduce 1 : 2 (the default role split's s16 : r16). */
+int RdcPlanReduceScatter(int n, size_t count, int dtype, size_t scratch_bytes, size_t tile_bytes, int max_blocks,
+                         uint64_t* out, int max_pieces, int* out_pieces);
+/* RdcPlanHbmBytes' model of one reduce-scatter, algo 2 (mesh: the scatter
+ * loads the other chunks and stores them remotely, the fold loads n x chunk r
+ * and stores it once) or 6 (direct: n x chunk r loaded, n-1 of them over the
+ * link, chunk r stored once).  out5 as RdcPlanHbmBytes; egress = the bytes of
+ * this rank's buffer that go to peers (pushed by it, or loaded by them). */
+int RdcPlanReduceScatterBytes(int n, size_t count, int dtype, int algo, uint64_t* out5);
 
 /* RdcPlanCoalesced: the staging image of one fusion group.  chunk_out (33
  * words): packed chunk offsets off[16], lengths len[16], total bytes.  units_out:

@@ -45,6 +45,12 @@ def _load():
         "RdcAllreduce": (i, [vp, sz, i, i, vp, vp]),
         "RdcBroadcast": (i, [vp, ctypes.c_ulong, i]),
         "RdcAllreduceOn": (i, [vp, vp, sz, i, i]),
+        "RdcReduceScatter": (i, [vp, sz, i, i]),
+        "RdcReduceScatterOn": (i, [vp, vp, sz, i, i]),
+        "RdcCommReduceScatter": (i, [vp, vp, sz, i, i, i, vp]),
+        "RdcPlanSplit": (i, [sz, i, i, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "RdcPlanReduceScatter": (i, [i, sz, i, sz, sz, i, ctypes.POINTER(u64), i, ctypes.POINTER(ctypes.c_int)]),
+        "RdcPlanReduceScatterBytes": (i, [i, sz, i, i, ctypes.POINTER(u64)]),
         "RdcAllgather": (i, [pvp, ctypes.POINTER(ctypes.c_size_t)]),
         "RdcAllgatherOn": (i, [vp, pvp, ctypes.POINTER(ctypes.c_size_t)]),
         "RdcCommAllgather": (i, [vp, pvp, ctypes.POINTER(ctypes.c_size_t), vp]),

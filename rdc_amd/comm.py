@@ -96,6 +96,24 @@ class Comm(object):
                                            _dev.dtype_enum(tensor.dtype), int(op), _ALGOS[algo], s))
         return tensor
 
+    def reduce_scatter(self, tensor, op, algo="auto", stream=None):
+        """In-place reduce-scatter of a contiguous ROCm tensor (RdcCommReduceScatter;
+        TryReduceScatterRing, communicator_collective.cc:115-182): chunk ``rank``
+        of ``split_range(tensor.numel(), world_size, rank)`` receives the
+        reduction, with the bits ``allreduce`` puts there; every other element
+        of ``tensor`` stays as passed.  Returns the flat view of that chunk.
+        ``algo``: "auto", "mesh" or "direct".  A contiguous numpy array is
+        reduced synchronously (RdcReduceScatterOn), in place likewise."""
+        from .core import host_reduce_scatter, split_range
+        if not _is_tensor(tensor):
+            return host_reduce_scatter(tensor, op, comm=self)
+        _dev._check_tensor(tensor)
+        s = stream if stream is not None else _dev.current_stream_ptr(tensor.device)
+        check_call(_LIB.RdcCommReduceScatter(self.handle, ctypes.c_void_p(tensor.data_ptr()), tensor.numel(),
+                                             _dev.dtype_enum(tensor.dtype), int(op), _ALGOS[algo], s))
+        lo, hi = split_range(tensor.numel(), self.world_size, self.rank)
+        return tensor.view(-1)[lo:hi]
+
     def allreduce_coalesced(self, tensors, op, algo="auto", stream=None):
         """Bucketed allreduce of a list of contiguous ROCm tensors of one dtype,
         in place: the result of ``allreduce`` on each tensor in order

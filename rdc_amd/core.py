@@ -164,6 +164,49 @@ def host_allreduce(data, op, prepare_fun=None, comm=None):
     return buf
 
 
+def split_range(count, n, rank):
+    """``(begin, end)``: the element range of chunk ``rank`` of
+    utils::Split(0, count, n) (include/utils/utils.h:59-70, RdcPlanSplit) — the
+    chunk a reduce-scatter leaves on that rank."""
+    lo, hi = ctypes.c_uint64(), ctypes.c_uint64()
+    check_call(_LIB.RdcPlanSplit(int(count), int(n), int(rank), ctypes.byref(lo), ctypes.byref(hi)))
+    return lo.value, hi.value
+
+
+def reduce_scatter(data, op):
+    """In-place reduce-scatter on the "main" communicator (RdcReduceScatter;
+    TryReduceScatterRing, communicator_collective.cc:115-182): chunk
+    ``get_rank()`` of ``split_range(data.size, get_world_size(), get_rank())``
+    receives the reduction — the bits ``allreduce`` puts there — and every
+    other element of ``data`` stays as passed.  A contiguous numpy.ndarray
+    (synchronous) or a ROCm torch.Tensor (stream-ordered on torch's current
+    stream); returns the flat view of this rank's chunk."""
+    op = int(Op(op) if not isinstance(op, Op) else op)
+    if type(data).__module__.startswith("torch"):
+        from . import comm as _comm
+        return _comm.get_comm("main").reduce_scatter(data, op)
+    return host_reduce_scatter(data, op)
+
+
+def host_reduce_scatter(data, op, comm=None):
+    """reduce_scatter of a host ndarray: RdcReduceScatter on "main", or
+    RdcReduceScatterOn on the Comm ``comm``."""
+    op = int(Op(op) if not isinstance(op, Op) else op)
+    if not isinstance(data, np.ndarray) or not data.flags.c_contiguous:
+        raise TypeError("reduce_scatter takes a contiguous numpy.ndarray or a torch.Tensor")
+    if data.dtype not in DTYPE_ENUM__:
+        raise TypeError("data type %s not supported" % str(data.dtype))
+    ptr = data.ctypes.data_as(ctypes.c_void_p)
+    if comm is not None:
+        check_call(_LIB.RdcReduceScatterOn(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], op))
+        n, r = comm.world_size, comm.rank
+    else:
+        check_call(_LIB.RdcReduceScatter(ptr, data.size, DTYPE_ENUM__[data.dtype], op))
+        n, r = get_world_size(), get_rank()
+    lo, hi = split_range(data.size, n, r)
+    return data.reshape(-1)[lo:hi]
+
+
 def allreduce_coalesced(arrays, op):
     """Bucketed allreduce of a list of arrays of one dtype, in place: the
     result of ``allreduce`` on each one (bit-identical), moved in fused device

@@ -371,6 +371,31 @@ void allreduce_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, i
     m.host->Allreduce(c, sendrecv, count, dtype, op, s);
 }
 
+// synchronous in-place reduce-scatter of host or device memory on communicator c
+void reduce_scatter_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, int dtype, int op) {
+    check_dtype_op(dtype, op);
+    if (c->size() == 1 || count == 0) return;
+    if (!sendrecv) throw std::invalid_argument("rdc: null buffer");
+    hipStream_t s = manager_stream(m, c->device());
+    if (is_device_pointer(sendrecv)) {
+        c->ReduceScatter(sendrecv, count, dtype, op, s);
+        c->Check(s);
+        return;
+    }
+    // host buffer: the whole input up, the device reduce-scatter, this rank's
+    // chunk back — no other byte of the host buffer is written
+    const size_t esz = rdc_dtype_size(dtype);
+    char* d = static_cast<char*>(staging(m, std::max<size_t>(count * esz, 256), c->device()));
+    hcheck(hipMemcpyAsync(d, sendrecv, count * esz, hipMemcpyHostToDevice, s), "H2D");
+    c->ReduceScatter(d, count, dtype, op, s);
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, c->size(), cb, ce);
+    const size_t lo = (size_t)cb[c->rank()] * esz, hi = (size_t)ce[c->rank()] * esz;
+    if (hi > lo)
+        hcheck(hipMemcpyAsync(static_cast<char*>(sendrecv) + lo, d + lo, hi - lo, hipMemcpyDeviceToHost, s), "D2H");
+    c->Check(s);
+}
+
 // synchronous coalesced allreduce of host or device buffers (all of one kind)
 void allreduce_coalesced_sync(Manager& m, Communicator* c, void** bufs, const size_t* counts, int nbuf, int dtype,
                               int op) {
@@ -498,6 +523,33 @@ int RdcAllreduce(void* sendrecv, size_t count, int dtype, int op, void (*prepare
         // world size 1: Communicator::Allreduce returns at once (communicator_base.h:133-138)
         if (m.world == 1 || count == 0) return;
         allreduce_sync(m, get_comm(m, "main", true), sendrecv, count, dtype, op);
+    });
+}
+
+int RdcReduceScatter(void* sendrecv, size_t count, int dtype, int op) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] {
+        require_init(m);
+        check_dtype_op(dtype, op);
+        // world size 1: chunk 0 is the whole buffer and already holds its own reduction
+        if (m.world == 1 || count == 0) return;
+        reduce_scatter_sync(m, get_comm(m, "main", true), sendrecv, count, dtype, op);
+    });
+}
+
+int RdcReduceScatterOn(void* comm, void* sendrecv, size_t count, int dtype, int op) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] { reduce_scatter_sync(m, as_comm(comm), sendrecv, count, dtype, op); });
+}
+
+int RdcCommReduceScatter(void* comm, void* dev_buf, size_t count, int dtype, int op, int algo, void* stream) {
+    return guard([&] {
+        if (algo != RDC_ALGO_AUTO && algo != RDC_ALGO_MESH && algo != RDC_ALGO_DIRECT)
+            throw std::invalid_argument("rdc: reduce-scatter has no schedule for algo " + std::to_string(algo) +
+                                        " (0 auto, 2 mesh, 6 direct)");
+        as_comm(comm)->ReduceScatter(dev_buf, count, dtype, op, static_cast<hipStream_t>(stream), algo);
     });
 }
 
@@ -778,6 +830,57 @@ int RdcPlanHbmBytes(int n, size_t count, int dtype, int algo, uint64_t* out5) {
         out5[2] = h.read_sum;
         out5[3] = h.write_sum;
         out5[4] = h.egress_max;
+    });
+}
+
+int RdcPlanSplit(size_t count, int n, int rank, uint64_t* begin, uint64_t* end) {
+    return guard([&] {
+        if (n < 1 || n > RDC_MAX_RANKS || rank < 0 || rank >= n || !begin || !end)
+            throw std::invalid_argument("rdc: bad argument");
+        int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+        SplitRanges((int64_t)count, n, cb, ce);
+        *begin = (uint64_t)cb[rank];
+        *end = (uint64_t)ce[rank];
+    });
+}
+
+int RdcPlanReduceScatterBytes(int n, size_t count, int dtype, int algo, uint64_t* out5) {
+    return guard([&] {
+        const size_t esz = rdc_dtype_size(dtype);
+        if (n < 1 || n > RDC_MAX_RANKS || esz == 0 || !out5 || (algo != RDC_ALGO_MESH && algo != RDC_ALGO_DIRECT))
+            throw std::invalid_argument("rdc: bad argument");
+        const HbmBytes h = ModelReduceScatterBytes(n, count, esz, algo);
+        out5[0] = h.read_max;
+        out5[1] = h.write_max;
+        out5[2] = h.read_sum;
+        out5[3] = h.write_sum;
+        out5[4] = h.egress_max;
+    });
+}
+
+int RdcPlanReduceScatter(int n, size_t count, int dtype, size_t scratch_bytes, size_t tile_bytes, int max_blocks,
+                         uint64_t* out, int max_pieces, int* out_pieces) {
+    return guard([&] {
+        const size_t esz = rdc_dtype_size(dtype);
+        if (n < 1 || n > RDC_MAX_RANKS || esz == 0 || !out_pieces) throw std::invalid_argument("rdc: bad argument");
+        const Layout L = MakeLayout(n, scratch_bytes ? scratch_bytes : CommConfig().scratch_bytes);
+        const std::vector<Piece> plan =
+            PlanReduceScatter(n, count, esz, L, tile_bytes, max_blocks > 0 ? max_blocks : 256);
+        *out_pieces = (int)plan.size();
+        for (int k = 0; k < (int)plan.size() && k < max_pieces && out; ++k) {
+            uint64_t* o = out + (size_t)k * RDC_PLAN_WORDS;
+            const Piece& p = plan[(size_t)k];
+            o[0] = p.tile_bytes;
+            o[1] = (uint64_t)p.nb_scatter;
+            o[2] = (uint64_t)p.nb_reduce;
+            o[3] = (uint64_t)p.nb_gather;
+            for (int c = 0; c < RDC_MAX_RANKS; ++c) {
+                o[4 + c] = p.off[c];
+                o[20 + c] = p.len[c];
+                o[36 + c] = p.mis[c];
+                o[52 + c] = (uint64_t)p.tiles[c];
+            }
+        }
     });
 }
 

@@ -1285,6 +1285,47 @@ void Communicator::Allreduce(void* buf, size_t count, int dtype, int op, hipStre
     LaunchRanges(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, algo, stream);
 }
 
+// TryReduceScatterRing (communicator_collective.cc:115-182; communicator_base.h:
+// 217-233: "after the function, node k get k-th segment of the reduction
+// result"), in place: chunk r of utils::Split(0, count, n) on rank r holds
+// x[r] (+) (x[r+1] (+) ... (+) x[r-1]) — the bits Allreduce's ring order puts
+// there — and every other byte of buf is left as the caller passed it (the
+// reference leaves ring partials there).  The ring order holds at every size:
+// the reference's reduce-scatter has no tree branch, so cfg_.ring_mincount is
+// not consulted.  Schedules: the registered-buffer one exactly where
+// DirectEligible takes it for an allreduce of these bytes, else the mesh's
+// first half (k_rscatter); a direct call that cannot run falls back to the
+// mesh on every rank.  DirectAuto's 16 / 32 MiB threshold was measured for
+// the allreduce and is PROVISIONAL here (DESIGN.md §7.4 records the sweep).
+void Communicator::ReduceScatter(void* buf, size_t count, int dtype, int op, hipStream_t stream, int algo) {
+    KernelSet ks;
+    if (!get_kernels(dtype, op, &ks))
+        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
+                                    std::to_string(op) + ")");
+    if (algo != RDC_ALGO_AUTO && algo != RDC_ALGO_MESH && algo != RDC_ALGO_DIRECT)
+        throw std::invalid_argument("rdc: reduce-scatter has no schedule for algo " + std::to_string(algo) +
+                                    " (0 auto, 2 mesh, 6 direct)");
+    const size_t esz = rdc_dtype_size(dtype);
+    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
+    if (n_ == 1 || count == 0) return;
+    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ChannelCall call(ch_.get(), stream);
+    const uint64_t nb = (uint64_t)count * esz;
+    if (DirectEligible(algo, nb, stream)) {
+        char* b0 = static_cast<char*>(buf);
+        if (AllreduceDirect(ks, &b0, &nb, 1, esz, stream, true)) return;
+    }
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
+    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
+    for (int c = 0; c < n_; ++c) {
+        off[c] = (uint64_t)cb[c] * esz;
+        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
+    }
+    LaunchReduceScatter(ks, static_cast<char*>(buf), off, len, nb, esz, stream);
+}
+
 // ------------------------------------------------- registered buffers ----
 // Every check here uses values identical on every rank (the schedule asked
 // for, the byte count, the channel kind, whether the stream is being
@@ -1783,7 +1824,8 @@ const Communicator::DirectTable& Communicator::DirectTableFor(const DirectDesc* 
 }
 
 bool Communicator::AllreduceDirect(const KernelSet& ks, char* const* bufs, const uint64_t* bytes, int nbuf,
-                                   size_t esz, hipStream_t stream) {
+                                   size_t esz, hipStream_t stream, bool rscatter) {
+    if (rscatter && nbuf != 1) throw std::logic_error("rdc: a direct reduce-scatter takes one buffer");
     Channel& ch = *ch_;
     const uint64_t call = ++ch.dcalls;  // the same on every rank (DirectEligible)
     DirectDesc* slots = reinterpret_cast<DirectDesc*>(ch.dreg.get()) + (call & 1) * (uint64_t)n_;
@@ -1884,7 +1926,7 @@ bool Communicator::AllreduceDirect(const KernelSet& ks, char* const* bufs, const
     a.rotate = direct_rotate() ? 1 : 0;
     const Shape sh = ShapeFor(total, RDC_ALGO_DIRECT);  // an Autotune'd grid, else the mesh's
     const int grid_cap = LaunchGrid(sh.max_blocks > 0 ? sh.max_blocks : mesh_blocks(),
-                                    ks.occupancy(RDC_KIND_DIRECT, n_));
+                                    ks.occupancy(rscatter ? RDC_KIND_RSCATTER_DIRECT : RDC_KIND_DIRECT, n_));
     // ~2 tiles (items) per block, 64 KiB .. 4 MiB, a multiple of 256 B
     uint64_t tile = total / n_ / (2 * (uint64_t)grid_cap) + 1;
     tile = std::min<uint64_t>(std::max<uint64_t>(tile, 64 << 10), 4 << 20);
@@ -1923,7 +1965,10 @@ bool Communicator::AllreduceDirect(const KernelSet& ks, char* const* bufs, const
     last_launch_[5] = RDC_ALGO_DIRECT;
     ++seq_;
     log_launch(this, seq_, RDC_ALGO_DIRECT, total, grid, tile);
-    hip_check(ks.direct(a, grid, stream), "launch direct allreduce");
+    // the reduce-scatter: the same ready / done protocol (a launch of kind
+    // RDC_KIND_DIRECT: peers read this buffer), owner r storing chunk r here only
+    if (rscatter) hip_check(ks.rscatter_direct(a, grid, stream), "launch direct reduce-scatter");
+    else hip_check(ks.direct(a, grid, stream), "launch direct allreduce");
     // the last launch that may read through this rank's peer mappings: a
     // later rendezvous that closes one of them waits for it first
     if (!ch.dlast) hip_check(hipEventCreateWithFlags(&ch.dlast, hipEventDisableTiming), "direct event");
@@ -2194,6 +2239,50 @@ void Communicator::LaunchRanges(const KernelSet& ks, char* buf, const uint64_t* 
         }
     }
     trace_ = nullptr;  // one call only
+}
+
+// The reduce-scatter's scratch schedule over the chunk byte ranges of `buf`:
+// PlanReduceScatterRanges' launches (the mesh's pieces and tiles, scatter and
+// reduce roles only) of k_rscatter, shaped like a mesh allreduce of `total`
+// bytes (RdcCommTune / RDC_NBLOCKS / RDC_TILE_BYTES apply), the grid clamped
+// by k_rscatter's own occupancy.
+void Communicator::LaunchReduceScatter(const KernelSet& ks, char* buf, const uint64_t* off, const uint64_t* len,
+                                       uint64_t total, size_t esz, hipStream_t stream) {
+    const Shape sh = ShapeFor(total, RDC_ALGO_MESH);
+    const int grid_cap =
+        LaunchGrid(sh.max_blocks > 0 ? sh.max_blocks : 2 * cus_min_, ks.occupancy(RDC_KIND_RSCATTER, n_));
+    const std::vector<Piece> plan =
+        PlanReduceScatterRanges(n_, off, len, esz, layout(), sh.tile_bytes, grid_cap, sh.split);
+    for (const Piece& p : plan) {
+        CollArgs a;
+        FillArgsCommon(&a);
+        if (&p == &plan.back()) {
+            a.notify = notify_;
+            a.notify_val = notify_val_;
+            notify_ = nullptr;
+        }
+        a.user = buf;
+        memcpy(a.off, p.off, sizeof(a.off));
+        memcpy(a.len, p.len, sizeof(a.len));
+        memcpy(a.mis, p.mis, sizeof(a.mis));
+        memcpy(a.tiles, p.tiles, sizeof(a.tiles));
+        a.tile_bytes = p.tile_bytes;
+        a.nb_scatter = p.nb_scatter;
+        a.nb_reduce = p.nb_reduce;
+        a.nb_gather = 0;
+        a.kind = RDC_KIND_RSCATTER;
+        ++seq_;
+        const int grid = p.nb_scatter + p.nb_reduce;
+        last_launch_[0] = (uint64_t)grid;
+        last_launch_[1] = (uint64_t)p.nb_scatter;
+        last_launch_[2] = (uint64_t)p.nb_reduce;
+        last_launch_[3] = 0;
+        last_launch_[4] = p.tile_bytes;
+        last_launch_[5] = RDC_ALGO_MESH;
+        log_launch(this, seq_, RDC_ALGO_MESH, total, grid, p.tile_bytes);
+        hip_check(ks.rscatter(a, grid, stream), "launch mesh reduce-scatter");
+    }
+    trace_ = nullptr;  // reduce-scatter launches are not traced
 }
 
 // Staging image of the coalesced path, grown on demand (never shrinks).  The

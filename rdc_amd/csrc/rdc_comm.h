@@ -230,6 +230,12 @@ public:
 
     // in-place device allreduce, stream-ordered; returns hipError_t-style code
     void Allreduce(void* buf, size_t count, int dtype, int op, hipStream_t stream, int algo = RDC_ALGO_AUTO);
+    // In-place device reduce-scatter, stream-ordered (TryReduceScatterRing,
+    // communicator_collective.cc:115-182): chunk `rank` of utils::Split(0,
+    // count, n) receives the reduction, in the ring's order at every size
+    // (no tree branch: rdc_reduce_ring_mincount does not apply); every other
+    // byte of buf stays as passed.  algo: auto, RDC_ALGO_MESH or RDC_ALGO_DIRECT.
+    void ReduceScatter(void* buf, size_t count, int dtype, int op, hipStream_t stream, int algo = RDC_ALGO_AUTO);
     // bucketed allreduce: the result of Allreduce on every buffer in order
     // (bit-identical), moved as fused launches over a chunk-major staging image
     void AllreduceCoalesced(void* const* bufs, const size_t* counts, int nbuf, int dtype, int op,
@@ -416,8 +422,12 @@ private:
     // rank decides alike)
     bool DirectEligible(int algo, uint64_t bytes, hipStream_t stream) const;
     // one buffer (nbuf = 1) or a coalesced list; bytes[b] > 0 for every b
+    // rscatter (nbuf = 1): the launch is the reduce-scatter's (k_rscatter_direct)
     bool AllreduceDirect(const KernelSet& ks, char* const* bufs, const uint64_t* bytes, int nbuf, size_t esz,
-                         hipStream_t stream);
+                         hipStream_t stream, bool rscatter = false);
+    // the scratch schedule of a reduce-scatter (k_rscatter) over chunk byte ranges of buf
+    void LaunchReduceScatter(const KernelSet& ks, char* buf, const uint64_t* off, const uint64_t* len, uint64_t total,
+                             size_t esz, hipStream_t stream);
     void TuneBuffer(size_t bytes);
     // fresh: the allocations exported in this call, as (index in me.alloc,
     // the canary: the first bytes of one of this call's buffers)

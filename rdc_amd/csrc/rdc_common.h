@@ -38,9 +38,13 @@ enum {
 
 // launch kinds (recorded on the device: the next launch reads the previous kind)
 // (tree launches use the one-shot's slot protocol and record RDC_KIND_ONESHOT;
-// RDC_KIND_TREE only names the kernel in occupancy queries)
+// RDC_KIND_TREE only names the kernel in occupancy queries; so does
+// RDC_KIND_RSCATTER_DIRECT: a reduce-scatter between registered buffers is a
+// launch of kind RDC_KIND_DIRECT.  RDC_KIND_RSCATTER: the mesh reduce-scatter,
+// whose launches end only after every peer's done word arrived)
 enum { RDC_KIND_NONE = 0, RDC_KIND_MESH = 1, RDC_KIND_RING = 2, RDC_KIND_BCAST = 3, RDC_KIND_ALLGATHER = 4,
-       RDC_KIND_ONESHOT = 5, RDC_KIND_TREE = 6, RDC_KIND_DIRECT = 7 };
+       RDC_KIND_ONESHOT = 5, RDC_KIND_TREE = 6, RDC_KIND_DIRECT = 7, RDC_KIND_RSCATTER = 8,
+       RDC_KIND_RSCATTER_DIRECT = 9 };
 
 #define RDC_MAX_RANKS 16
 // 64-bit words from one hand-off flag to the next: 1 = packed (the default);
@@ -106,7 +110,7 @@ struct CollArgs {
     char* ag[RDC_MAX_RANKS];             // rank p's allgather scratch region
     uint64_t* flags[RDC_MAX_RANKS];      // rank p's flag region: [2n][max_tiles] + done[n] (rdc_device.h seq)
     char* cbuf[RDC_MAX_RANKS];           // allgather: local buffer of rank c's data (off/len index into it)
-    int nb_scatter, nb_reduce, nb_gather;  // mesh block roles (allgather: push / -, gather)
+    int nb_scatter, nb_reduce, nb_gather;  // mesh block roles (allgather: push / -, gather; reduce-scatter: no gather)
     uint32_t* err;                       // local device error word
     uint32_t* err_mirror;                // host-pinned copy of *err, refreshed by every launch's last block
     uint32_t* notify;                    // optional pinned word: the last block stores notify_val there when

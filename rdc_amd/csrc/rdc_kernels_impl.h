@@ -178,7 +178,8 @@ __global__ __launch_bounds__(kBlock) void k_reduce_unaligned(char* dst, const ch
 // tile, written to the local user buffer and to every peer's allgather slot.
 // one element at byte offset e of the tile: ring-order fold of the n ranks'
 // values, stored to the local user buffer and every peer's allgather slot
-template <int OP, typename T>
+// (kPush false: the reduce-scatter's fold — the local user buffer only)
+template <int OP, typename T, bool kPush = true>
 __device__ __forceinline__ void mesh_fold_elem(const CollArgs& a, char* own, const char* slot0, uint64_t soff,
                                                uint64_t e) {
     const int n = a.n, r = a.rank, f = a.fold[r];  // the ring order of chunk f
@@ -189,21 +190,23 @@ __device__ __forceinline__ void mesh_fold_elem(const CollArgs& a, char* own, con
     T acc = val((f - 1 + n) % n);
     for (int k = 2; k <= n; ++k) acc = OpF<OP>::apply(val((f - k + n) % n), acc);
     *reinterpret_cast<T*>(own + e) = acc;
-    for (int p = 0; p < n; ++p)
-        if (p != r) st_elem_wt<T>(a.ag[p] + soff + e, acc);
+    if (kPush)
+        for (int p = 0; p < n; ++p)
+            if (p != r) st_elem_wt<T>(a.ag[p] + soff + e, acc);
 }
 
 // Fold `tlen` bytes: own (this rank's values, overwritten with the result),
 // slot0 (rank q's copy at slot0 + q*slot_bytes) in ring order; the result also
-// goes to every peer's allgather region at byte offset soff.
-template <int OP, typename T, int NMAX>
+// goes to every peer's allgather region at byte offset soff (kPush; without
+// it — k_rscatter — nothing leaves this rank and soff is unused).
+template <int OP, typename T, int NMAX, bool kPush = true>
 __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, const char* slot0, uint64_t soff, uint64_t tlen) {
     const int n = a.n, r = a.rank, f = a.fold[r];
     const unsigned tid = threadIdx.x;
     if ((((uintptr_t)own ^ (uintptr_t)slot0) & 15) != 0) {
         // this rank's buffer is not 16-B aligned: exact, element by element
         for (uint64_t e = (uint64_t)tid * sizeof(T); e < tlen; e += (uint64_t)kBlock * sizeof(T))
-            mesh_fold_elem<OP, T>(a, own, slot0, soff, e);
+            mesh_fold_elem<OP, T, kPush>(a, own, slot0, soff, e);
         return;
     }
     const uint64_t mis16 = (uint64_t)(uintptr_t)own & 15;
@@ -213,8 +216,8 @@ __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, 
     const uint64_t tail = head + (nvec << 4);
     {   // element-wise head / tail (< 16 bytes each)
         const uint64_t nh = head / sizeof(T), nt = (tlen - tail) / sizeof(T);
-        if (tid < nh) mesh_fold_elem<OP, T>(a, own, slot0, soff, tid * sizeof(T));
-        else if (tid >= 64 && tid - 64 < nt) mesh_fold_elem<OP, T>(a, own, slot0, soff, tail + (tid - 64) * sizeof(T));
+        if (tid < nh) mesh_fold_elem<OP, T, kPush>(a, own, slot0, soff, tid * sizeof(T));
+        else if (tid >= 64 && tid - 64 < nt) mesh_fold_elem<OP, T, kPush>(a, own, slot0, soff, tail + (tid - 64) * sizeof(T));
     }
     // All n contributions of U positions are loaded before folding (NMAX x U
     // 16-B loads in flight per lane); folding one rank at a time inside a
@@ -226,9 +229,11 @@ __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, 
     __amdgpu_buffer_rsrc_t ag_rs[NMAX];
     for (uint64_t ib = 0; ib < nvec; ib += U * stride) {
         const uint64_t i = ib + tid;
+        if (kPush) {
 #pragma unroll
-        for (int p = 0; p < NMAX; ++p)
-            if (p < n && p != r) ag_rs[p] = wt_rsrc(a.ag[p] + soff + head + ib * 16);
+            for (int p = 0; p < NMAX; ++p)
+                if (p < n && p != r) ag_rs[p] = wt_rsrc(a.ag[p] + soff + head + ib * 16);
+        }
         v4u v[U][NMAX];
         bool live[U];
 #pragma unroll
@@ -258,9 +263,11 @@ __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, 
                 if (k <= n) acc = reduce16<OP, T>(v[u][k - 1], acc);
             const uint64_t b = head + (i + u * stride) * 16;
             st16(own + b, acc);
+            if (kPush) {
 #pragma unroll
-            for (int p = 0; p < NMAX; ++p)
-                if (p < n && p != r) st16_wt(ag_rs[p], (uint32_t)((tid + u * stride) * 16), acc);
+                for (int p = 0; p < NMAX; ++p)
+                    if (p < n && p != r) st16_wt(ag_rs[p], (uint32_t)((tid + u * stride) * 16), acc);
+            }
         }
     }
 }
@@ -419,6 +426,69 @@ __device__ __forceinline__ void mesh_body(const CollArgs& a, uint64_t seq) {
         if (a.poison) {
             __syncthreads();
             block_poison(src + toff, tlen);
+        }
+    }
+}
+
+// ================================================= mesh reduce-scatter ===
+// TryReduceScatterRing's result (communicator_collective.cc:115-182: "node k
+// get k-th segment of the reduction result") by the mesh's first half: the
+// scatter role as in mesh_body, the reduce role folding chunk r in its ring
+// order into the local user buffer ONLY.  No allgather slots, no second
+// hand-off, no gather role: every byte of the user buffer outside chunk r
+// stays as the caller passed it (the scatter only reads it).
+// Slot reuse: an allreduce's rank finishes only after gathering results each
+// owner produced after reading its RS slots; here nothing comes back, so the
+// launch itself ends only once every peer's done word for it arrived
+// (launch_done<true>) — every owner has then read its slots, and no later
+// launch of any kind needs a gate of its own.
+template <int OP, typename T, int NMAX>
+__device__ __forceinline__ void rscatter_body(const CollArgs& a, uint64_t seq) {
+    const int n = a.n, r = a.rank;
+    Abort ab{a.err, wall_clock64() + a.timeout_ticks, a.poll_rmw};
+    int b = blockIdx.x;
+    int tmax = 0;
+    for (int c = 0; c < n; ++c) tmax = a.tiles[c] > tmax ? a.tiles[c] : tmax;
+    __shared__ uint64_t* s_flags[RDC_MAX_RANKS];
+
+    if (b < a.nb_scatter) {
+        // ---- scatter: my copy of chunk c's tile t -> owner c's rs slot r
+        const int items = (n - 1) * tmax;
+        // the same slots as the mesh's scatter, so the same gate: after a
+        // one-shot launch the owners may still be reading their RS slots
+        if (b < items && prev_kind(a) == RDC_KIND_ONESHOT &&
+            !gate_on_peers(a, seq, r + 1, n - 1, ab, RDC_KERR_TIMEOUT_RS))
+            return;
+        for (int it = b; it < items; it += a.nb_scatter) {
+            const int t = it / (n - 1);
+            const int c = (r + 1 + it % (n - 1)) % n;
+            if (t >= a.tiles[c]) continue;
+            const uint64_t toff = (uint64_t)t * a.tile_bytes;
+            uint64_t tlen = a.len[c] - toff;
+            if (tlen > a.tile_bytes) tlen = a.tile_bytes;
+            char* dst = a.rs[c] + (uint64_t)r * a.slot_bytes + a.mis[c];
+            block_copy<kDstPeer>(dst + toff, a.user + a.off[c] + toff, tlen);
+            block_publish1(flag_word(a, c, (uint64_t)r * a.max_tiles + t), seq, a.uc);
+        }
+        return;
+    }
+    b -= a.nb_scatter;
+    // ---- reduce: chunk r, tile t, once all n-1 contributions landed
+    for (int t = b; t < a.tiles[r]; t += a.nb_reduce) {
+        if (threadIdx.x < (unsigned)(n - 1)) {
+            const int p = (r + 1 + threadIdx.x) % n;
+            s_flags[threadIdx.x] = flag_word(a, r, (uint64_t)p * a.max_tiles + t);
+        }
+        __syncthreads();
+        if (!block_wait(s_flags, n - 1, seq, ab, RDC_KERR_TIMEOUT_RS, a.uc)) return;
+        const uint64_t toff = (uint64_t)t * a.tile_bytes;
+        uint64_t tlen = a.len[r] - toff;
+        if (tlen > a.tile_bytes) tlen = a.tile_bytes;
+        mesh_reduce_range<OP, T, NMAX, false>(a, a.user + a.off[r] + toff, a.rs[r] + a.mis[r] + toff, 0, tlen);
+        if (a.poison) {  // every peer's copy of this tile was read
+            __syncthreads();
+            for (int k = 1; k < n; ++k)
+                block_poison(a.rs[r] + (uint64_t)((r + k) % n) * a.slot_bytes + a.mis[r] + toff, tlen);
         }
     }
 }
@@ -636,7 +706,10 @@ __device__ __forceinline__ void mesh_pull_body(const CollArgs& a, uint64_t seq) 
 //          stream moves on.
 // Fold order per element: chunk r's ring order, as every schedule.  All ranks'
 // buffers are congruent mod 16 (checked at the rendezvous), so one 16-B path.
-template <int OP, typename T, int NMAX>
+// kAll false (k_rscatter_direct, the reduce-scatter): the result goes to this
+// rank's buffer only — chunk r of it is read by owner r alone, so the in-place
+// store races with nothing, and no other byte of any buffer is written.
+template <int OP, typename T, int NMAX, bool kAll = true>
 __device__ __forceinline__ void direct_fold_range(const CollArgs& a, char* const* buf, uint64_t tlen) {
     const int n = a.n, r = a.rank, f = a.fold[r];
     const unsigned tid = threadIdx.x;
@@ -648,7 +721,7 @@ __device__ __forceinline__ void direct_fold_range(const CollArgs& a, char* const
         for (int k = 2; k <= n; ++k) acc = OpF<OP>::apply(val((f - k + n) % n), acc);
         for (int q = 0; q < n; ++q) {
             if (q == r) *reinterpret_cast<T*>(buf[q] + e) = acc;
-            else st_elem_wt<T>(buf[q] + e, acc);
+            else if (kAll) st_elem_wt<T>(buf[q] + e, acc);
         }
     };
     const uint64_t mis16 = (uint64_t)(uintptr_t)buf[r] & 15;
@@ -701,7 +774,7 @@ __device__ __forceinline__ void direct_fold_range(const CollArgs& a, char* const
 #pragma unroll
                 for (int u = 0; u < U; ++u)
                     if (live[u]) st16_nt(buf[r] + head + (i + u * stride) * 16, v[u][0]);
-            } else {
+            } else if (kAll) {
                 const __amdgpu_buffer_rsrc_t rs = wt_rsrc(buf[q] + head + ib * 16);
 #pragma unroll
                 for (int u = 0; u < U; ++u)
@@ -711,7 +784,7 @@ __device__ __forceinline__ void direct_fold_range(const CollArgs& a, char* const
     }
 }
 
-template <int OP, typename T, int NMAX>
+template <int OP, typename T, int NMAX, bool kAll = true>
 __device__ __forceinline__ void direct_body(const CollArgs& a, uint64_t seq) {
     const int n = a.n, r = a.rank;
     Abort ab{a.err, wall_clock64() + a.timeout_ticks, a.poll_rmw};
@@ -726,7 +799,7 @@ __device__ __forceinline__ void direct_body(const CollArgs& a, uint64_t seq) {
     __syncthreads();
     if (!block_wait(s_flags, n - 1, seq, ab, RDC_KERR_TIMEOUT_RS, a.uc)) return;
     __shared__ char* s_tile[RDC_MAX_RANKS];
-    if (a.units) {
+    if (kAll && a.units) {  // (the reduce-scatter takes one buffer)
         // coalesced list: item t = piece of chunk r of buffer it[0], at byte
         // it[1], it[2] bytes; rank q's buffer b at ptr[q * dnbuf + b]
         const uint64_t* items = static_cast<const uint64_t*>(a.units);
@@ -739,7 +812,7 @@ __device__ __forceinline__ void direct_body(const CollArgs& a, uint64_t seq) {
             if (threadIdx.x < (unsigned)n)
                 s_tile[threadIdx.x] = reinterpret_cast<char*>(ptr[(uint64_t)threadIdx.x * a.dnbuf + b]) + so;
             __syncthreads();
-            direct_fold_range<OP, T, NMAX>(a, s_tile, tlen);
+            direct_fold_range<OP, T, NMAX, kAll>(a, s_tile, tlen);
             __syncthreads();  // s_tile is rewritten for the next item
         }
         return;
@@ -758,7 +831,7 @@ __device__ __forceinline__ void direct_body(const CollArgs& a, uint64_t seq) {
         if (tlen > a.tile_bytes) tlen = a.tile_bytes;
         if (threadIdx.x < (unsigned)n) s_tile[threadIdx.x] = s_buf[threadIdx.x] + toff;
         __syncthreads();
-        direct_fold_range<OP, T, NMAX>(a, s_tile, tlen);
+        direct_fold_range<OP, T, NMAX, kAll>(a, s_tile, tlen);
         __syncthreads();  // s_tile is rewritten for the next tile
     }
 }
@@ -1209,6 +1282,9 @@ __device__ void bcast_body(const CollArgs& a, uint64_t seq) {
 // buffer writes through the kernel boundary).  A launch that writes host
 // memory (zero-copy host path: `notify`) or uses cached scratch keeps the
 // system-scope fences, so the host reads the results after the notify word.
+// kWaitPeers (k_rscatter): the launch also ends only after every peer's done
+// word for it arrived, as a direct launch does — see rscatter_body.
+template <bool kWaitPeers = false>
 __device__ __forceinline__ void launch_done(const CollArgs& a, uint64_t seq) {
     const bool fence = a.notify != nullptr || !a.uc;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1232,10 +1308,12 @@ __device__ __forceinline__ void launch_done(const CollArgs& a, uint64_t seq) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             for (int p = 0; p < a.n; ++p)
                 if (p != a.rank) flag_store(done_word(a, p, a.rank), seq);
-            if (a.kind == RDC_KIND_DIRECT) {
+            if (kWaitPeers || a.kind == RDC_KIND_DIRECT) {
                 // registered buffers: every owner finished writing into this
                 // rank's buffer before its stream moves on (done words of this
-                // launch from every peer; bounded like every wait)
+                // launch from every peer; bounded like every wait).  Mesh
+                // reduce-scatter: every owner finished reading its RS slots
+                // before this rank's next launch may write them
                 const uint64_t deadline = wall_clock64() + a.timeout_ticks;
                 bool gave_up = false;
                 for (int p = 0; p < a.n && !gave_up; ++p) {
@@ -1324,6 +1402,23 @@ template <int OP, typename T, int NMAX>
 __global__ __launch_bounds__(kBlock) void k_direct(CollArgs a) {
     uint64_t seq;
     if (!launch_begin(a, &seq)) direct_body<OP, T, NMAX>(a, seq);
+    launch_done(a, seq);
+}
+
+// reduce-scatter, scratch schedule (RDC_KIND_RSCATTER)
+template <int OP, typename T, int NMAX>
+__global__ __launch_bounds__(kBlock) void k_rscatter(CollArgs a) {
+    uint64_t seq;
+    if (!launch_begin(a, &seq)) rscatter_body<OP, T, NMAX>(a, seq);
+    launch_done<true>(a, seq);
+}
+
+// reduce-scatter between registered buffers (a launch of kind RDC_KIND_DIRECT:
+// peers read this rank's buffer, so launch_done waits for them as for k_direct)
+template <int OP, typename T, int NMAX>
+__global__ __launch_bounds__(kBlock) void k_rscatter_direct(CollArgs a) {
+    uint64_t seq;
+    if (!launch_begin(a, &seq)) direct_body<OP, T, NMAX, false>(a, seq);
     launch_done(a, seq);
 }
 
@@ -1755,6 +1850,20 @@ struct Kernels {
             hipLaunchKernelGGL((k_direct<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
         return hipGetLastError();
     }
+    static hipError_t rscatter(const CollArgs& a, int grid, hipStream_t s) {
+        if (a.n <= 8)
+            hipLaunchKernelGGL((k_rscatter<OP, T, 8>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
+        else
+            hipLaunchKernelGGL((k_rscatter<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
+        return hipGetLastError();
+    }
+    static hipError_t rscatter_direct(const CollArgs& a, int grid, hipStream_t s) {
+        if (a.n <= 8)
+            hipLaunchKernelGGL((k_rscatter_direct<OP, T, 8>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
+        else
+            hipLaunchKernelGGL((k_rscatter_direct<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
+        return hipGetLastError();
+    }
     static hipError_t ring(const CollArgs& a, int grid, hipStream_t s) {
         hipLaunchKernelGGL((k_ring<OP, T>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
         return hipGetLastError();
@@ -1779,13 +1888,16 @@ struct Kernels {
         return hipGetLastError();
     }
     static int occupancy(int kind, int n) {
-        // [mesh 8, mesh 16, oneshot 8, oneshot 16, ring, tree 8, tree 16, direct 8, direct 16]; 0 = not queried yet
-        static int cache[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        // [mesh 8, mesh 16, oneshot 8, oneshot 16, ring, tree 8, tree 16, direct 8, direct 16,
+        //  rscatter 8, rscatter 16, rscatter direct 8, rscatter direct 16]; 0 = not queried yet
+        static int cache[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         const int wide = n > 8 ? 1 : 0;
         const int slot = kind == RDC_KIND_RING      ? 4
                          : kind == RDC_KIND_TREE    ? 5 + wide
                          : kind == RDC_KIND_ONESHOT ? 2 + wide
                          : kind == RDC_KIND_DIRECT  ? 7 + wide
+                         : kind == RDC_KIND_RSCATTER ? 9 + wide
+                         : kind == RDC_KIND_RSCATTER_DIRECT ? 11 + wide
                                                     : wide;
         if (cache[slot] > 0) return cache[slot];
         int b = 0;
@@ -1799,6 +1911,10 @@ struct Kernels {
             case 6: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_tree<OP, T, 16>, kBlock, debug_lds_pad()); break;
             case 7: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_direct<OP, T, 8>, kBlock, debug_lds_pad()); break;
             case 8: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_direct<OP, T, 16>, kBlock, debug_lds_pad()); break;
+            case 9: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter<OP, T, 8>, kBlock, debug_lds_pad()); break;
+            case 10: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter<OP, T, 16>, kBlock, debug_lds_pad()); break;
+            case 11: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter_direct<OP, T, 8>, kBlock, debug_lds_pad()); break;
+            case 12: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter_direct<OP, T, 16>, kBlock, debug_lds_pad()); break;
             default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_ring<OP, T>, kBlock, debug_lds_pad()); break;
         }
         if (e != hipSuccess || b <= 0) {
@@ -1816,6 +1932,8 @@ struct Kernels {
     ks->mesh = &Kernels<OP, T>::mesh;     \
     ks->ring = &Kernels<OP, T>::ring;     \
     ks->direct = &Kernels<OP, T>::direct; \
+    ks->rscatter = &Kernels<OP, T>::rscatter; \
+    ks->rscatter_direct = &Kernels<OP, T>::rscatter_direct; \
     ks->oneshot = &Kernels<OP, T>::oneshot; \
     ks->tree = &Kernels<OP, T>::tree;       \
     ks->svc = &Kernels<OP, T>::svc;         \

@@ -141,6 +141,36 @@ std::vector<Piece> PlanAllreduce(int n, uint64_t count, size_t esz, const Layout
     return PlanAllreduceRanges(n, off, len, esz, L, algo, cfg_tile, max_blocks);
 }
 
+std::vector<Piece> PlanReduceScatterRanges(int n, const uint64_t* off, const uint64_t* len, size_t esz,
+                                           const Layout& L, size_t cfg_tile, int max_blocks, MeshSplit split) {
+    std::vector<Piece> out = PlanAllreduceRanges(n, off, len, esz, L, RDC_ALGO_MESH, cfg_tile, max_blocks, split);
+    const int s16 = std::min(std::max(split.s16, 1), 14), r16 = std::min(std::max(split.r16, 1), 15 - s16);
+    const int G = std::max(2, max_blocks);
+    for (Piece& p : out) {
+        int T = 0;
+        for (int c = 0; c < n; ++c) T = std::max(T, p.tiles[c]);
+        // the gather role's share goes to the two roles left, s16 : r16
+        const int s = std::min(std::max(G * s16 / (s16 + r16), 1), G - 1);
+        p.nb_scatter = std::max(1, std::min((n - 1) * T, s));
+        p.nb_reduce = std::max(1, std::min(T, G - s));
+        p.nb_gather = 0;
+    }
+    return out;
+}
+
+std::vector<Piece> PlanReduceScatter(int n, uint64_t count, size_t esz, const Layout& L, size_t cfg_tile,
+                                     int max_blocks, MeshSplit split) {
+    if (n <= 1 || count == 0 || esz == 0) return std::vector<Piece>();
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, n, cb, ce);
+    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
+    for (int c = 0; c < n; ++c) {
+        off[c] = (uint64_t)cb[c] * esz;
+        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
+    }
+    return PlanReduceScatterRanges(n, off, len, esz, L, cfg_tile, max_blocks, split);
+}
+
 uint64_t OneshotHalfBytes(const Layout& L) { return round_down(L.slot_bytes / 2, RDC_SLOT_ALIGN); }
 
 bool OneshotEligible(int n, uint64_t bytes, const Layout& L, uint64_t push_max) {
@@ -469,6 +499,37 @@ HbmBytes ModelHbmBytes(int n, uint64_t count, size_t esz, int algo) {
             rd += (uint64_t)(n - 1) * S + (uint64_t)n * S;
             wr += (uint64_t)(n - 1) * S + S;
             eg += (uint64_t)(n - 1) * S;
+        }
+        h.read_max = std::max(h.read_max, rd);
+        h.write_max = std::max(h.write_max, wr);
+        h.read_sum += rd;
+        h.write_sum += wr;
+        h.egress_max = std::max(h.egress_max, eg);
+    }
+    return h;
+}
+
+// One in-place reduce-scatter, in ModelHbmBytes' conventions (a remote access
+// counted at the rank that issues it), per the loops of k_rscatter /
+// k_rscatter_direct:
+//   mesh:   scatter every other chunk to its owner (load user, store remote:
+//           egress); fold own chunk (load n-1 slots + user, store user)
+//   direct: owner r loads chunk r of all n user buffers, n-1 of them over the
+//           link (egress = what the peers load from this rank's buffer), and
+//           stores it once, into its own buffer
+HbmBytes ModelReduceScatterBytes(int n, uint64_t count, size_t esz, int algo) {
+    HbmBytes h;
+    if (n < 2 || count == 0) return h;
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, n, cb, ce);
+    const uint64_t S = count * esz;
+    for (int r = 0; r < n; ++r) {
+        const uint64_t own = (uint64_t)(ce[r] - cb[r]) * esz, others = S - own;
+        uint64_t rd = (uint64_t)n * own, wr = own;
+        const uint64_t eg = others;  // mesh: pushed to the owners; direct: loaded by them
+        if (algo != RDC_ALGO_DIRECT) {
+            rd += others;
+            wr += others;
         }
         h.read_max = std::max(h.read_max, rd);
         h.write_max = std::max(h.write_max, wr);

@@ -102,6 +102,11 @@ int AutoAlgo(int n, uint64_t bytes, const Layout& L, uint64_t push_max);
 // 0.117 vs pull mesh 0.103 ms at 4 MiB, 0.142 vs 0.164 at 16 MiB, 0.81 vs
 // 1.92 at 256 MiB; n = 2 direct 0.0315 vs ring 0.0258 ms at 16 MiB, 0.064 vs
 // 0.090 at 64 MiB.
+// The reduce-scatter (Communicator::ReduceScatter) inherits this rule as it
+// stands; for it the threshold is PROVISIONAL — measured for the allreduce
+// only.  Its own sweep (profiles/reduce_scatter/): direct
+// overtakes the mesh between 16 and 64 MiB at n = 4, by 16 MiB at n = 8, and
+// the two are level up to 64 MiB at n = 2.
 constexpr uint64_t kDirectMinAuto = ~(uint64_t)0;
 constexpr uint64_t kDirectAutoMinBytes = (uint64_t)16 << 20;
 constexpr uint64_t kDirectAutoMinBytes2 = (uint64_t)32 << 20;
@@ -125,6 +130,20 @@ std::vector<Piece> PlanAllreduceRanges(int n, const uint64_t* off, const uint64_
                                        MeshSplit split = MeshSplit());
 Piece PlanOneshotRanges(int n, const uint64_t* off, const uint64_t* len, uint64_t total, const Layout& L,
                         size_t cfg_tile, int max_blocks);
+
+// ------------------------------------------------------ reduce-scatter ---
+// In-place reduce-scatter (TryReduceScatterRing, communicator_collective.cc:
+// 115-182): the launches of the scratch schedule (k_rscatter).  The pieces are
+// PlanAllreduceRanges' for the mesh — same slots, mis, tiles and the cutting
+// of chunks beyond one slot — with no gather role: nb_gather = 0, and the
+// grid is split between scatter and reduce in the ratio s16 : r16 of the
+// configured MeshSplit (default 4 : 8 = 1/3 scatter, 2/3 reduce), each role
+// holding at least one block and no more blocks than it has items.
+std::vector<Piece> PlanReduceScatterRanges(int n, const uint64_t* off, const uint64_t* len, size_t esz,
+                                           const Layout& L, size_t cfg_tile, int max_blocks,
+                                           MeshSplit split = MeshSplit());
+std::vector<Piece> PlanReduceScatter(int n, uint64_t count, size_t esz, const Layout& L, size_t cfg_tile,
+                                     int max_blocks, MeshSplit split = MeshSplit());
 
 // ------------------------------------------------------ tree allreduce ---
 // rdc_reduce_ring_mincount (communicator_manager.cc:46): TryAllreduce takes
@@ -189,5 +208,7 @@ struct HbmBytes {
     uint64_t read_max = 0, write_max = 0, read_sum = 0, write_sum = 0, egress_max = 0;
 };
 HbmBytes ModelHbmBytes(int n, uint64_t count, size_t esz, int algo);
+// The same model of one reduce-scatter (algo RDC_ALGO_MESH or RDC_ALGO_DIRECT)
+HbmBytes ModelReduceScatterBytes(int n, uint64_t count, size_t esz, int algo);
 
 }  // namespace rdc_amd

@@ -8,6 +8,12 @@ half), 5 = pull-mode mesh, 6 = direct (registered buffers).  SWEEP_ALGOS
 (e.g. "0/1/6") picks the schedules.  Direct-schedule calls also report the
 host side of their rendezvous per call (<name>_rendezvous_us: publish, map,
 confirm; <name>_export_us: the export step alone; max over ranks).
+SWEEP_COLLECTIVE=reduce_scatter times RdcCommReduceScatter instead, algos 0 / 2 /
+6 (rs_auto, rs_mesh, rs_direct), and in the same run the allreduce's mesh and
+direct schedules as the yardstick (allreduce_mesh, allreduce_direct); next to
+the direct entry, rs_direct_hbm_fraction = the modelled HBM bytes (read + write,
+the most of any rank) of the direct reduce-scatter over the direct allreduce's
+(RdcPlanReduceScatterBytes / RdcPlanHbmBytes).
 
     python -m torch.distributed.run --nproc-per-node N tools/algo_sweep.py [sizes_MiB] [steps]
 """
@@ -39,19 +45,29 @@ def main():
     big = int(max(sizes) * (1 << 20))
     buf = torch.empty(big // 4, dtype=torch.float32, device="cuda")
     rdc_amd.fill_(buf, 0x5EED0000, rank)
+    rs_mode = os.environ.get("SWEEP_COLLECTIVE", "allreduce") == "reduce_scatter"
     out = {}
     for mib in sizes:
         nb = int(mib * (1 << 20))
         row = {}
-        for algo, name in ((0, "auto"), (1, "ring"), (2, "mesh"), (3, "oneshot"), (5, "mesh_pull"), (6, "direct")):
-            if str(algo) not in os.environ.get("SWEEP_ALGOS", "0/1/2/3").replace(",", "/").split("/"):
-                continue
+        if rs_mode:
+            entries = [(True, 0, "rs_auto"), (True, 2, "rs_mesh"), (True, 6, "rs_direct"),
+                       (False, 2, "allreduce_mesh"), (False, 6, "allreduce_direct")]
+        else:
+            entries = [(False, algo, name) for algo, name in ((0, "auto"), (1, "ring"), (2, "mesh"), (3, "oneshot"),
+                                                              (5, "mesh_pull"), (6, "direct"))
+                       if str(algo) in os.environ.get("SWEEP_ALGOS", "0/1/2/3").replace(",", "/").split("/")]
+        for scatter, algo, name in entries:
             if algo == 3 and nb > half.value // 2:
                 continue
 
             def one():
-                check_call(_LIB.RdcCommAllreduceEx(comm.handle, ctypes.c_void_p(buf.data_ptr()), nb // 4, 6, 2, algo,
-                                                   sp))
+                if scatter:
+                    check_call(_LIB.RdcCommReduceScatter(comm.handle, ctypes.c_void_p(buf.data_ptr()), nb // 4, 6, 2,
+                                                         algo, sp))
+                else:
+                    check_call(_LIB.RdcCommAllreduceEx(comm.handle, ctypes.c_void_p(buf.data_ptr()), nb // 4, 6, 2,
+                                                       algo, sp))
 
             def stats():
                 r = {}
@@ -78,7 +94,7 @@ def main():
             ll = (ctypes.c_uint64 * 6)()
             check_call(_LIB.RdcCommLastLaunch(comm.handle, ll))
             if algo == 0:  # the schedule the automatic choice launched
-                row["auto_schedule"] = {1: "ring", 2: "mesh", 3: "oneshot", 4: "tree", 5: "mesh_pull",
+                row["rs_auto_schedule" if scatter else "auto_schedule"] = {1: "ring", 2: "mesh", 3: "oneshot", 4: "tree", 5: "mesh_pull",
                                         6: "direct"}.get(int(ll[5]), int(ll[5]))
             d1 = stats()
             if d1["direct_calls"] > d0["direct_calls"]:  # host side of the direct rendezvous, per call (max over ranks)
@@ -88,9 +104,15 @@ def main():
                 dist.all_reduce(v, op=dist.ReduceOp.MAX)
                 row[name + "_rendezvous_us"] = round(float(v[0]), 2)
                 row[name + "_export_us"] = round(float(v[1]), 2)
+        if rs_mode:
+            m, full = (ctypes.c_uint64 * 5)(), (ctypes.c_uint64 * 5)()
+            check_call(_LIB.RdcPlanReduceScatterBytes(world, nb // 4, 6, 6, m))
+            check_call(_LIB.RdcPlanHbmBytes(world, nb // 4, 6, 6, full))
+            row["rs_direct_hbm_fraction"] = round((m[0] + m[1]) / float(full[0] + full[1]), 4)
         out["%g MiB" % mib] = row
     if rank == 0:
-        print(json.dumps({"algo_sweep_ms_per_launch": out, "world": world, "ranks_share_gpu": True,
+        print(json.dumps({"algo_sweep_ms_per_launch": out, "world": world,
+                          "collective": "reduce_scatter" if rs_mode else "allreduce", "ranks_share_gpu": True,
                           "RDC_DIRECT_BYTES": os.environ.get("RDC_DIRECT_BYTES", "auto (default)")}), flush=True)
     dist.barrier()
     rdc_amd.finalize()
