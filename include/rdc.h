@@ -367,6 +367,20 @@ public:
         }
         Allgather(p.data(), sz.data());
     }
+    /*! \brief out-of-place all-to-all, equal split (MI355X addition; host or
+     *  device memory): bytes [p * bytes_per_peer, +bytes_per_peer) of send land
+     *  at [rank * bytes_per_peer, +bytes_per_peer) of rank p's recv (RdcAlltoall) */
+    virtual void Alltoall(const void* send, void* recv, size_t bytes_per_peer) {
+        detail::Check(RdcAlltoallOn(handle_, send, recv, bytes_per_peer), "Alltoall");
+    }
+    /*! \brief all-to-all with per-peer byte offsets and lengths (arrays of
+     *  GetWorldSize() entries; MI355X addition): send_len[p] here equals
+     *  recv_len[GetRank()] on rank p; one segment is at most RdcPlanAlltoallCap
+     *  bytes (RdcAlltoallv) */
+    virtual void Alltoallv(const void* send, const size_t* send_off, const size_t* send_len, void* recv,
+                           const size_t* recv_off, const size_t* recv_len) {
+        detail::Check(RdcAlltoallvOn(handle_, send, send_off, send_len, recv, recv_off, recv_len), "Alltoallv");
+    }
     /*! \brief non-blocking point-to-point (communicator.h:69-80); host or device
      *  memory; messages on one (src, dst) pair match in order, equal sizes */
     virtual WorkCompletion* ISend(const void* sendaddr, uint64_t size_in_bytes, int dest) {
@@ -637,6 +651,38 @@ inline std::pair<uint64_t, uint64_t> ReduceScatter(DType* sendrecvbuf, uint64_t 
     uint64_t lo = 0, hi = 0;
     detail::Check(RdcPlanSplit(count, c->GetWorldSize(), c->GetRank(), &lo, &hi), "ReduceScatter");
     return std::pair<uint64_t, uint64_t>(lo, hi);
+}
+
+/*! \brief out-of-place all-to-all, equal split (MI355X addition to the public
+ *  surface: the reference has no personalised exchange).  Elements
+ *  [p * count_per_rank, +count_per_rank) of send land at [r * count_per_rank,
+ *  +count_per_rank) of rank p's recv (r = this rank); send and recv hold
+ *  GetWorldSize() * count_per_rank elements and must not overlap */
+template <typename DType>
+inline void Alltoall(const DType* send, DType* recv, uint64_t count_per_rank,
+                     const std::string& comm_name = kMainCommName) {
+    GetCommunicator(comm_name)->Alltoall(send, recv, count_per_rank * sizeof(DType));
+}
+
+/*! \brief all-to-all with per-peer counts and displacements, in elements
+ *  (MI355X addition; MPI_Alltoallv's arguments): send_counts[p] elements at
+ *  send + send_displs[p] go to rank p, which receives them at recv +
+ *  recv_displs[r]; send_counts[p] here equals recv_counts[r] on rank p.  One
+ *  segment is at most RdcPlanAlltoallCap bytes: slice larger exchanges */
+template <typename DType>
+inline void Alltoallv(const DType* send, const uint64_t* send_counts, const uint64_t* send_displs, DType* recv,
+                      const uint64_t* recv_counts, const uint64_t* recv_displs,
+                      const std::string& comm_name = kMainCommName) {
+    comm::ICommunicator* c = GetCommunicator(comm_name);
+    const size_t n = (size_t)c->GetWorldSize();
+    std::vector<size_t> so(n), sl(n), ro(n), rl(n);
+    for (size_t p = 0; p < n; ++p) {
+        so[p] = (size_t)send_displs[p] * sizeof(DType);
+        sl[p] = (size_t)send_counts[p] * sizeof(DType);
+        ro[p] = (size_t)recv_displs[p] * sizeof(DType);
+        rl[p] = (size_t)recv_counts[p] * sizeof(DType);
+    }
+    c->Alltoallv(send, so.data(), sl.data(), recv, ro.data(), rl.data());
 }
 
 /*! \brief in-place allreduce of a typed Buffer (include/api.h:65-66; declared

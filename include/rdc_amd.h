@@ -104,6 +104,42 @@ int RdcAllgatherOn(void* comm, void** bufs, const size_t* sizes);
 int RdcReduceScatter(void* sendrecv, size_t count, int dtype, int op);
 int RdcReduceScatterOn(void* comm, void* sendrecv, size_t count, int dtype, int op);
 
+/* All-to-all, out of place (MI355X addition: the reference has no personalised
+ * exchange; its custom-reducer allreduce builds one out of ISend / IRecv).
+ * On rank r, bytes [send_off[p], send_off[p] + send_len[p]) of `send` land at
+ * [recv_off[r], recv_off[r] + recv_len[r]) of rank p's `recv`; arrays of n
+ * entries, offsets and lengths in bytes.  Contract, as in MPI: send_len[p] on
+ * rank r equals recv_len[r] on rank p — a rank cannot check it.  A
+ * violation never hangs or faults and never leaves the slot or the receive
+ * segment, but only one kind of it is reported: a receiver that expects more
+ * tiles than were sent ends in the bounded-wait error (RDC_TIMEOUT).  Where
+ * the sender's length is the longer one (or the tile counts happen to be
+ * equal) every expected tile arrives, and the receiver lands recv_len[r] bytes
+ * of undefined content — a truncated segment — with no error.  Rank r's own segment is a local copy (send_len[r] must equal
+ * recv_len[r]).  Zero-length segments are legal, a whole zero row or column
+ * and an all-zero call included: an alltoallv is still collective and is
+ * exactly ONE device launch.  After the call every byte of `recv` outside the
+ * n receive segments is as the caller left it and `send` is unchanged.
+ * Refused before anything is launched: a null buffer with bytes to move, send
+ * and receive ranges that overlap (each side's extent is the hull of its
+ * segments), receive segments that overlap each other, own-segment lengths
+ * that differ, and a segment longer than one launch carries
+ * (RdcPlanAlltoallCap: about 255 MiB at 8 ranks with the default scratch).
+ * The refusal is local: the peers of a rank that refused report the
+ * bounded-wait error, as for any call not made collectively; callers slice
+ * larger exchanges.  RdcAlltoall is the equal split, segment p at
+ * p * bytes_per_peer on both sides, any size (every rank cuts the same
+ * ceil(bytes_per_peer / cap) launches; none for 0 bytes).
+ * Host or device memory (detected; host buffers are staged through HBM like
+ * RdcAllgather's); synchronous.  World size 1: the own-segment copy only (no
+ * GPU needed for host memory).  RdcAlltoall[v] use the "main" communicator. */
+int RdcAlltoall(const void* send, void* recv, size_t bytes_per_peer);
+int RdcAlltoallOn(void* comm, const void* send, void* recv, size_t bytes_per_peer);
+int RdcAlltoallv(const void* send, const size_t* send_off, const size_t* send_len, void* recv,
+                 const size_t* recv_off, const size_t* recv_len);
+int RdcAlltoallvOn(void* comm, const void* send, const size_t* send_off, const size_t* send_len, void* recv,
+                   const size_t* recv_off, const size_t* recv_len);
+
 /* Coalesced (bucketed) allreduce: the result of one RdcAllreduce per buffer,
  * in order, bit-identical, but the buffers move in fused launches (BASELINE
  * cfg5 / test/mallreduce.cc's back-to-back shape).  A list takes the schedule
@@ -235,6 +271,19 @@ int RdcCommAllreduceCoalesced(void* comm, void* const* dev_bufs, const size_t* c
 int RdcCommBroadcast(void* comm, void* dev_buf, size_t bytes, int root, void* stream);
 /* device-resident allgather of per-rank buffers (see RdcAllgather), stream-ordered */
 int RdcCommAllgather(void* comm, void** dev_bufs, const size_t* sizes, void* stream);
+/* Device-resident all-to-all (see RdcAlltoall / RdcAlltoallv for the result,
+ * the contract and the refusals), stream-ordered; the scratch path (k_alltoall:
+ * every rank pushes segment p into peer p's allgather slot `rank` and lands its
+ * own slots; works in single-process groups).  The image of a segment starts at
+ * its slot's base, so the 16-B vector path runs on a side whose segment address
+ * is 16-B aligned and the narrower word paths otherwise.  Capture in a
+ * hipGraph is untested.  RdcCommAlltoallv is exactly one launch per call (an all-zero call
+ * included); RdcCommLastLaunch then reports {grid, push blocks, 0, land blocks,
+ * tile bytes, 102}.  The offset / length arrays are read before the call
+ * returns. */
+int RdcCommAlltoall(void* comm, const void* send, void* recv, size_t bytes_per_peer, void* stream);
+int RdcCommAlltoallv(void* comm, const void* send, const size_t* send_off, const size_t* send_len, void* recv,
+                     const size_t* recv_off, const size_t* recv_len, void* stream);
 /* synchronise `stream` and report any device-side collective failure */
 int RdcCommCheck(void* comm, void* stream);
 /* A communicator's parameter: "rdc_reduce_ring_mincount", "RDC_SCRATCH_BYTES",
@@ -462,6 +511,25 @@ int RdcPlanReduceScatter(int n, size_t count, int dtype, size_t scratch_bytes, s
  * link, chunk r stored once).  out5 as RdcPlanHbmBytes; egress = the bytes of
  * this rank's buffer that go to peers (pushed by it, or loaded by them). */
 int RdcPlanReduceScatterBytes(int n, size_t count, int dtype, int algo, uint64_t* out5);
+
+/* The one launch of an all-to-all as rank `rank` plans it from its row
+ * (send_len[n]) and column (recv_len[n]) of the size matrix.  out (36 words):
+ * tile bytes, push blocks, land blocks, 0, then out_tiles[16] (tiles of the
+ * segment for rank p; 0 for p = rank) and in_tiles[16] (tiles of the segment
+ * from rank c; [rank]: the own segment's).  Tile bytes depend only on values
+ * equal on every rank (tile_bytes, else 64 KiB; with equal_len != 0 — the
+ * equal split's bytes per peer of this launch — one push item per push block
+ * within [64 KiB, 1 MiB]), and a pair's tiles on the one length both ends
+ * know, so sender and receiver cut alike. */
+int RdcPlanAlltoall(int n, int rank, const uint64_t* send_len, const uint64_t* recv_len, size_t scratch_bytes,
+                    size_t tile_bytes, int max_blocks, uint64_t equal_len, uint64_t* out36);
+/* the largest segment one all-to-all launch carries: the allgather's per-piece
+ * capacity, round_down(slot_bytes - 256, 256) of RdcPlanLayout(n, scratch_bytes) */
+int RdcPlanAlltoallCap(int n, size_t scratch_bytes, uint64_t* cap);
+/* RdcPlanHbmBytes' model of one all-to-all on rank `rank`: reads = the send
+ * buffer + its own slots, writes = the peers' slots + the receive buffer,
+ * egress = the bytes pushed to peers (out5 as RdcPlanHbmBytes; max = sum) */
+int RdcPlanAlltoallBytes(int n, int rank, const uint64_t* send_len, const uint64_t* recv_len, uint64_t* out5);
 
 /* RdcPlanCoalesced: the staging image of one fusion group.  chunk_out (33
  * words): packed chunk offsets off[16], lengths len[16], total bytes.  units_out:

@@ -51,6 +51,17 @@ def _load():
         "RdcPlanSplit": (i, [sz, i, i, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "RdcPlanReduceScatter": (i, [i, sz, i, sz, sz, i, ctypes.POINTER(u64), i, ctypes.POINTER(ctypes.c_int)]),
         "RdcPlanReduceScatterBytes": (i, [i, sz, i, i, ctypes.POINTER(u64)]),
+        "RdcAlltoall": (i, [vp, vp, sz]),
+        "RdcAlltoallOn": (i, [vp, vp, vp, sz]),
+        "RdcAlltoallv": (i, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+        "RdcAlltoallvOn": (i, [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp, ctypes.POINTER(sz),
+                               ctypes.POINTER(sz)]),
+        "RdcCommAlltoall": (i, [vp, vp, vp, sz, vp]),
+        "RdcCommAlltoallv": (i, [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp, ctypes.POINTER(sz),
+                                 ctypes.POINTER(sz), vp]),
+        "RdcPlanAlltoall": (i, [i, i, ctypes.POINTER(u64), ctypes.POINTER(u64), sz, sz, i, u64, ctypes.POINTER(u64)]),
+        "RdcPlanAlltoallCap": (i, [i, sz, ctypes.POINTER(u64)]),
+        "RdcPlanAlltoallBytes": (i, [i, i, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "RdcAllgather": (i, [pvp, ctypes.POINTER(ctypes.c_size_t)]),
         "RdcAllgatherOn": (i, [vp, pvp, ctypes.POINTER(ctypes.c_size_t)]),
         "RdcCommAllgather": (i, [vp, pvp, ctypes.POINTER(ctypes.c_size_t), vp]),

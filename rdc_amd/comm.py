@@ -56,6 +56,34 @@ _ALGOS = {"auto": ALGO_AUTO, "ring": ALGO_RING, "mesh": ALGO_MESH, "oneshot": AL
           "mesh_pull": ALGO_MESH_PULL, "direct": ALGO_DIRECT}
 
 
+def _a2a_equal_counts(nsend, nrecv, n):
+    if nsend != nrecv or nsend % n:
+        raise ValueError("rdc_amd: all_to_all needs send and recv of one size divisible by the world size")
+    return [nsend // n] * n
+
+
+def _a2a_bytes(n, send_counts, send_displs, recv_counts, recv_displs, esz, nsend, nrecv):
+    """The four byte arrays of RdcAlltoallv from counts / displacements in
+    elements (displacements default to the prefix sums); segments must lie
+    inside their buffers."""
+    out = []
+    for counts, displs, total in ((send_counts, send_displs, nsend), (recv_counts, recv_displs, nrecv)):
+        counts = [int(c) for c in counts]
+        if len(counts) != n:
+            raise ValueError("rdc_amd: all_to_all_v needs one count per rank")
+        if displs is None:
+            displs = [sum(counts[:p]) for p in range(n)]
+        displs = [int(d) for d in displs]
+        if len(displs) != n:
+            raise ValueError("rdc_amd: all_to_all_v needs one displacement per rank")
+        for c, d in zip(counts, displs):
+            if c < 0 or d < 0 or (c and d + c > total):
+                raise ValueError("rdc_amd: all_to_all_v segment outside its buffer")
+        out.append((ctypes.c_size_t * n)(*[d * esz for d in displs]))
+        out.append((ctypes.c_size_t * n)(*[c * esz for c in counts]))
+    return out
+
+
 class Comm(object):
     """A communicator handle.  Collectives are in place on device memory and
     stream-ordered (torch's current stream unless ``stream`` is given)."""
@@ -156,6 +184,49 @@ class Comm(object):
         s = stream if stream is not None else _dev.current_stream_ptr(tensors[0].device)
         check_call(_LIB.RdcCommAllgather(self.handle, ptrs, sizes, s))
         return tensors
+
+    def all_to_all(self, send, recv, stream=None):
+        """Out-of-place all-to-all, equal split (RdcCommAlltoall): ``send`` and
+        ``recv`` are contiguous ROCm tensors of equal size divisible by the
+        world size; part p of ``send`` lands in part ``rank`` of rank p's
+        ``recv``.  Stream-ordered; returns ``recv``.  Contiguous numpy arrays
+        take the blocking host entry (RdcAlltoallOn)."""
+        n = self.world_size
+        if not _is_tensor(send) or not _is_tensor(recv):
+            from .core import host_all_to_all
+            return host_all_to_all(send, recv, comm=self)
+        _dev._check_tensor(send)
+        _dev._check_tensor(recv)
+        if send.dtype != recv.dtype:
+            raise ValueError("rdc_amd: all_to_all needs one dtype")
+        cnt = _a2a_equal_counts(send.numel(), recv.numel(), n)
+        s = stream if stream is not None else _dev.current_stream_ptr(send.device)
+        check_call(_LIB.RdcCommAlltoall(self.handle, ctypes.c_void_p(send.data_ptr()), ctypes.c_void_p(recv.data_ptr()),
+                                        cnt[0] * send.element_size(), s))
+        return recv
+
+    def all_to_all_v(self, send, send_counts, recv, recv_counts, send_displs=None, recv_displs=None, stream=None):
+        """All-to-all with per-peer counts, in elements (RdcCommAlltoallv):
+        ``send_counts[p]`` elements at ``send_displs[p]`` of ``send`` go to rank
+        p, which receives them at its ``recv_displs[rank]``; the displacements
+        default to the prefix sums of the counts.  ``send_counts[p]`` here must
+        equal ``recv_counts[rank]`` on rank p.  One launch per call; a segment
+        is at most the launch capacity (RdcPlanAlltoallCap) — slice larger
+        exchanges.  Contiguous ROCm tensors (stream-ordered) or numpy arrays
+        (blocking, RdcAlltoallvOn); returns ``recv``."""
+        if not _is_tensor(send) or not _is_tensor(recv):
+            from .core import host_all_to_all_v
+            return host_all_to_all_v(send, send_counts, recv, recv_counts, send_displs, recv_displs, comm=self)
+        _dev._check_tensor(send)
+        _dev._check_tensor(recv)
+        if send.dtype != recv.dtype:
+            raise ValueError("rdc_amd: all_to_all_v needs one dtype")
+        so, sl, ro, rl = _a2a_bytes(self.world_size, send_counts, send_displs, recv_counts, recv_displs,
+                                    send.element_size(), send.numel(), recv.numel())
+        s = stream if stream is not None else _dev.current_stream_ptr(send.device)
+        check_call(_LIB.RdcCommAlltoallv(self.handle, ctypes.c_void_p(send.data_ptr()), so, sl,
+                                         ctypes.c_void_p(recv.data_ptr()), ro, rl, s))
+        return recv
 
     # ----------------------------------------------------- point-to-point --
     def isend(self, buf, dest_rank):

@@ -207,6 +207,70 @@ def host_reduce_scatter(data, op, comm=None):
     return data.reshape(-1)[lo:hi]
 
 
+def all_to_all(send, recv):
+    """Out-of-place all-to-all on the "main" communicator, equal split: part p
+    of ``send`` lands in part ``get_rank()`` of rank p's ``recv``.  Contiguous
+    numpy.ndarrays (synchronous, RdcAlltoall) or ROCm torch.Tensors
+    (stream-ordered on torch's current stream) of equal size divisible by the
+    world size; returns ``recv``."""
+    if type(send).__module__.startswith("torch"):
+        from . import comm as _comm
+        return _comm.get_comm("main").all_to_all(send, recv)
+    return host_all_to_all(send, recv)
+
+
+def host_all_to_all(send, recv, comm=None):
+    """all_to_all of host ndarrays: RdcAlltoall on "main", or RdcAlltoallOn on
+    the Comm ``comm`` (any size: the library cuts the launches)."""
+    from .comm import _a2a_equal_counts
+    for a in (send, recv):
+        if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
+            raise TypeError("all_to_all takes contiguous numpy.ndarrays or torch.Tensors")
+    if send.dtype != recv.dtype:
+        raise TypeError("all_to_all needs one dtype")
+    n = comm.world_size if comm is not None else get_world_size()
+    nbytes = _a2a_equal_counts(send.size, recv.size, n)[0] * send.itemsize
+    sp, rp = send.ctypes.data_as(ctypes.c_void_p), recv.ctypes.data_as(ctypes.c_void_p)
+    if comm is not None:
+        check_call(_LIB.RdcAlltoallOn(comm.handle, sp, rp, nbytes))
+    else:
+        check_call(_LIB.RdcAlltoall(sp, rp, nbytes))
+    return recv
+
+
+def all_to_all_v(send, send_counts, recv, recv_counts, send_displs=None, recv_displs=None):
+    """All-to-all with per-peer counts on the "main" communicator
+    (RdcAlltoallv), counts and displacements in elements, displacements
+    defaulting to the prefix sums: ``send_counts[p]`` elements at
+    ``send_displs[p]`` go to rank p, which receives them at its
+    ``recv_displs[get_rank()]``.  numpy.ndarrays (synchronous) or ROCm
+    torch.Tensors (stream-ordered); returns ``recv``."""
+    if type(send).__module__.startswith("torch"):
+        from . import comm as _comm
+        return _comm.get_comm("main").all_to_all_v(send, send_counts, recv, recv_counts, send_displs, recv_displs)
+    return host_all_to_all_v(send, send_counts, recv, recv_counts, send_displs, recv_displs)
+
+
+def host_all_to_all_v(send, send_counts, recv, recv_counts, send_displs=None, recv_displs=None, comm=None):
+    """all_to_all_v of host ndarrays: RdcAlltoallv on "main", or RdcAlltoallvOn
+    on the Comm ``comm``."""
+    from .comm import _a2a_bytes
+    for a in (send, recv):
+        if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
+            raise TypeError("all_to_all takes contiguous numpy.ndarrays or torch.Tensors")
+    if send.dtype != recv.dtype:
+        raise TypeError("all_to_all needs one dtype")
+    n = comm.world_size if comm is not None else get_world_size()
+    so, sl, ro, rl = _a2a_bytes(n, send_counts, send_displs, recv_counts, recv_displs, send.itemsize, send.size,
+                                recv.size)
+    sp, rp = send.ctypes.data_as(ctypes.c_void_p), recv.ctypes.data_as(ctypes.c_void_p)
+    if comm is not None:
+        check_call(_LIB.RdcAlltoallvOn(comm.handle, sp, so, sl, rp, ro, rl))
+    else:
+        check_call(_LIB.RdcAlltoallv(sp, so, sl, rp, ro, rl))
+    return recv
+
+
 def allreduce_coalesced(arrays, op):
     """Bucketed allreduce of a list of arrays of one dtype, in place: the
     result of ``allreduce`` on each one (bit-identical), moved in fused device

@@ -485,7 +485,155 @@ void allgather_sync(Manager& m, Communicator* c, void** bufs, const size_t* size
     c->Check(s);
 }
 
+// synchronous alltoallv of host or device memory on communicator c (offsets and
+// lengths as 64-bit arrays of n entries)
+void alltoallv_sync(Manager& m, Communicator* c, const void* send, const uint64_t* soff, const uint64_t* slen,
+                    void* recv, const uint64_t* roff, const uint64_t* rlen) {
+    const int n = c->size(), r = c->rank();
+    const char* why = CheckAlltoallv(n, r, send, soff, slen, recv, roff, rlen, c->AlltoallCap());
+    if (*why) throw std::invalid_argument(why);
+    uint64_t slo = ~(uint64_t)0, shi = 0, rlo = ~(uint64_t)0, rhi = 0;  // hulls of the non-empty segments
+    for (int p = 0; p < n; ++p) {
+        if (slen[p]) slo = std::min(slo, soff[p]), shi = std::max(shi, soff[p] + slen[p]);
+        if (rlen[p]) rlo = std::min(rlo, roff[p]), rhi = std::max(rhi, roff[p] + rlen[p]);
+    }
+    const bool sdev = shi == 0 || is_device_pointer(static_cast<const char*>(send) + slo);
+    const bool rdev = rhi == 0 || is_device_pointer(static_cast<char*>(recv) + rlo);
+    if (n == 1) {  // the own segment only; host memory needs no GPU
+        if (!slen[0]) return;
+        if (sdev && rdev) {
+            hipStream_t s = manager_stream(m, c->device());
+            c->Alltoallv(send, soff, slen, recv, roff, rlen, s);
+            hcheck(hipStreamSynchronize(s), "stream sync");
+        } else if (!sdev && !rdev) {
+            memcpy(static_cast<char*>(recv) + roff[0], static_cast<const char*>(send) + soff[0], slen[0]);
+        } else {
+            hcheck(hipMemcpy(static_cast<char*>(recv) + roff[0], static_cast<const char*>(send) + soff[0], slen[0],
+                             hipMemcpyDefault), "copy");
+        }
+        return;
+    }
+    hipStream_t s = manager_stream(m, c->device());
+    if (sdev && rdev) {
+        c->Alltoallv(send, soff, slen, recv, roff, rlen, s);
+        c->Check(s);
+        return;
+    }
+    // host memory: the send hull up into one staging image, the exchange between
+    // the images, every receive SEGMENT back — no other byte of recv is written
+    const uint64_t sbytes = shi ? shi - slo : 0, rbytes = rhi ? rhi - rlo : 0;
+    const size_t rat = (size_t)((sbytes + 255) / 256 * 256);
+    char* d = static_cast<char*>(staging(m, std::max<size_t>(rat + rbytes, 256), c->device()));
+    uint64_t so[RDC_MAX_RANKS] = {0}, ro[RDC_MAX_RANKS] = {0};
+    for (int p = 0; p < n; ++p) {
+        so[p] = slen[p] ? soff[p] - slo : 0;
+        ro[p] = rlen[p] ? roff[p] - rlo : 0;
+    }
+    if (sbytes)
+        hcheck(hipMemcpyAsync(d, static_cast<const char*>(send) + slo, sbytes, hipMemcpyDefault, s), "H2D");
+    c->Alltoallv(d, so, slen, d + rat, ro, rlen, s);
+    for (int p = 0; p < n; ++p)
+        if (rlen[p])
+            hcheck(hipMemcpyAsync(static_cast<char*>(recv) + roff[p], d + rat + ro[p], rlen[p], hipMemcpyDefault, s),
+                   "D2H");
+    c->Check(s);
+}
+
+void alltoallv_sync_sz(Manager& m, Communicator* c, const void* send, const size_t* soff, const size_t* slen,
+                       void* recv, const size_t* roff, const size_t* rlen) {
+    if (!soff || !slen || !roff || !rlen) throw std::invalid_argument("rdc: all-to-all: null offset or length array");
+    uint64_t a[4][RDC_MAX_RANKS] = {{0}};
+    for (int p = 0; p < c->size(); ++p) {
+        a[0][p] = soff[p];
+        a[1][p] = slen[p];
+        a[2][p] = roff[p];
+        a[3][p] = rlen[p];
+    }
+    alltoallv_sync(m, c, send, a[0], a[1], recv, a[2], a[3]);
+}
+
+// the equal split: pieces of at most the capacity, the same cut on every rank
+void alltoall_sync(Manager& m, Communicator* c, const void* send, void* recv, size_t bytes_per_peer) {
+    const int n = c->size();
+    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
+    for (int p = 0; p < n; ++p) {
+        off[p] = (uint64_t)p * bytes_per_peer;
+        len[p] = bytes_per_peer;
+    }
+    const char* why = CheckAlltoallv(n, c->rank(), send, off, len, recv, off, len, 0);
+    if (*why) throw std::invalid_argument(why);
+    if (bytes_per_peer == 0) return;
+    if (n > 1 && is_device_pointer(send) && is_device_pointer(recv)) {
+        hipStream_t s = manager_stream(m, c->device());
+        c->Alltoall(send, recv, bytes_per_peer, s);
+        c->Check(s);
+        return;
+    }
+    const uint64_t cap = c->AlltoallCap();
+    for (uint64_t b0 = 0; b0 < bytes_per_peer; b0 += cap) {
+        uint64_t poff[RDC_MAX_RANKS] = {0}, plen[RDC_MAX_RANKS] = {0};
+        for (int p = 0; p < n; ++p) {
+            poff[p] = off[p] + b0;
+            plen[p] = std::min<uint64_t>(cap, bytes_per_peer - b0);
+        }
+        alltoallv_sync(m, c, send, poff, plen, recv, poff, plen);
+    }
+}
+
 }  // namespace
+
+int RdcAlltoall(const void* send, void* recv, size_t bytes_per_peer) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] {
+        require_init(m);
+        alltoall_sync(m, get_comm(m, "main", true), send, recv, bytes_per_peer);
+    });
+}
+
+int RdcAlltoallOn(void* comm, const void* send, void* recv, size_t bytes_per_peer) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] { alltoall_sync(m, as_comm(comm), send, recv, bytes_per_peer); });
+}
+
+int RdcAlltoallv(const void* send, const size_t* send_off, const size_t* send_len, void* recv, const size_t* recv_off,
+                 const size_t* recv_len) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] {
+        require_init(m);
+        alltoallv_sync_sz(m, get_comm(m, "main", true), send, send_off, send_len, recv, recv_off, recv_len);
+    });
+}
+
+int RdcAlltoallvOn(void* comm, const void* send, const size_t* send_off, const size_t* send_len, void* recv,
+                   const size_t* recv_off, const size_t* recv_len) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] { alltoallv_sync_sz(m, as_comm(comm), send, send_off, send_len, recv, recv_off, recv_len); });
+}
+
+int RdcCommAlltoall(void* comm, const void* send, void* recv, size_t bytes_per_peer, void* stream) {
+    return guard([&] { as_comm(comm)->Alltoall(send, recv, bytes_per_peer, static_cast<hipStream_t>(stream)); });
+}
+
+int RdcCommAlltoallv(void* comm, const void* send, const size_t* send_off, const size_t* send_len, void* recv,
+                     const size_t* recv_off, const size_t* recv_len, void* stream) {
+    return guard([&] {
+        Communicator* c = as_comm(comm);
+        if (!send_off || !send_len || !recv_off || !recv_len)
+            throw std::invalid_argument("rdc: all-to-all: null offset or length array");
+        uint64_t a[4][RDC_MAX_RANKS] = {{0}};
+        for (int p = 0; p < c->size(); ++p) {
+            a[0][p] = send_off[p];
+            a[1][p] = send_len[p];
+            a[2][p] = recv_off[p];
+            a[3][p] = recv_len[p];
+        }
+        c->Alltoallv(send, a[0], a[1], recv, a[2], a[3], static_cast<hipStream_t>(stream));
+    });
+}
 
 int RdcAllgather(void** bufs, const size_t* sizes) {
     Manager& m = M();
@@ -881,6 +1029,45 @@ int RdcPlanReduceScatter(int n, size_t count, int dtype, size_t scratch_bytes, s
                 o[52 + c] = (uint64_t)p.tiles[c];
             }
         }
+    });
+}
+
+int RdcPlanAlltoall(int n, int rank, const uint64_t* send_len, const uint64_t* recv_len, size_t scratch_bytes,
+                    size_t tile_bytes, int max_blocks, uint64_t equal_len, uint64_t* out36) {
+    return guard([&] {
+        if (n < 1 || n > RDC_MAX_RANKS || rank < 0 || rank >= n || !send_len || !recv_len || !out36)
+            throw std::invalid_argument("rdc: bad argument");
+        const Layout L = MakeLayout(n, scratch_bytes ? scratch_bytes : CommConfig().scratch_bytes);
+        const AlltoallPlan P =
+            PlanAlltoall(n, rank, send_len, recv_len, L, tile_bytes, max_blocks > 0 ? max_blocks : 256, equal_len);
+        out36[0] = P.tile_bytes;
+        out36[1] = (uint64_t)P.nb_push;
+        out36[2] = (uint64_t)P.nb_land;
+        out36[3] = 0;
+        for (int p = 0; p < RDC_MAX_RANKS; ++p) {
+            out36[4 + p] = (uint64_t)P.out_tiles[p];
+            out36[20 + p] = (uint64_t)P.in_tiles[p];
+        }
+    });
+}
+
+int RdcPlanAlltoallCap(int n, size_t scratch_bytes, uint64_t* cap) {
+    return guard([&] {
+        if (n < 1 || n > RDC_MAX_RANKS || !cap) throw std::invalid_argument("rdc: bad argument");
+        *cap = AlltoallCap(MakeLayout(n, scratch_bytes ? scratch_bytes : CommConfig().scratch_bytes));
+    });
+}
+
+int RdcPlanAlltoallBytes(int n, int rank, const uint64_t* send_len, const uint64_t* recv_len, uint64_t* out5) {
+    return guard([&] {
+        if (n < 1 || n > RDC_MAX_RANKS || rank < 0 || rank >= n || !send_len || !recv_len || !out5)
+            throw std::invalid_argument("rdc: bad argument");
+        const HbmBytes h = ModelAlltoallBytes(n, rank, send_len, recv_len);
+        out5[0] = h.read_max;
+        out5[1] = h.write_max;
+        out5[2] = h.read_sum;
+        out5[3] = h.write_sum;
+        out5[4] = h.egress_max;
     });
 }
 

@@ -2846,6 +2846,99 @@ void Communicator::Allgather(void* const* bufs, const uint64_t* sizes, hipStream
     }
 }
 
+// ------------------------------------------------------------ all-to-all ----
+// The personalised exchange (MI355X addition; k_alltoall):
+// scratch path only, out of place.  A rank sees only its row and column of the
+// size matrix while launch numbers are global, so an alltoallv is exactly one
+// launch whatever its lengths (all zero included), and everything both ends
+// of a pair must agree on comes from values every rank has (PlanAlltoall).
+uint64_t Communicator::AlltoallCap() const {
+    return rdc_amd::AlltoallCap(n_ == 1 ? MakeLayout(1, cfg_.scratch_bytes) : layout());
+}
+
+void Communicator::Alltoallv(const void* send, const uint64_t* send_off, const uint64_t* send_len, void* recv,
+                             const uint64_t* recv_off, const uint64_t* recv_len, hipStream_t stream) {
+    const char* why = CheckAlltoallv(n_, rank_, send, send_off, send_len, recv, recv_off, recv_len, AlltoallCap());
+    if (*why) throw std::invalid_argument(why);
+    if (n_ == 1) {  // the own segment only
+        if (send_len[0])
+            hip_check(hipMemcpyAsync(static_cast<char*>(recv) + recv_off[0],
+                                     static_cast<const char*>(send) + send_off[0], send_len[0], hipMemcpyDefault,
+                                     stream),
+                      "all-to-all own segment");
+        return;
+    }
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ChannelCall call(ch_.get(), stream);
+    LaunchAlltoall(static_cast<const char*>(send), send_off, send_len, static_cast<char*>(recv), recv_off, recv_len, 0,
+                   stream);
+}
+
+void Communicator::Alltoall(const void* send, void* recv, uint64_t bytes_per_peer, hipStream_t stream) {
+    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
+    for (int p = 0; p < n_; ++p) {
+        off[p] = (uint64_t)p * bytes_per_peer;
+        len[p] = bytes_per_peer;
+    }
+    const char* why = CheckAlltoallv(n_, rank_, send, off, len, recv, off, len, 0);
+    if (*why) throw std::invalid_argument(why);
+    if (bytes_per_peer == 0) return;  // known on every rank: nothing is launched anywhere
+    if (n_ == 1) {
+        hip_check(hipMemcpyAsync(recv, send, bytes_per_peer, hipMemcpyDefault, stream), "all-to-all own segment");
+        return;
+    }
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ChannelCall call(ch_.get(), stream);
+    // every rank knows bytes_per_peer, so every rank cuts the same pieces
+    const uint64_t cap = AlltoallCap();
+    for (uint64_t b0 = 0; b0 < bytes_per_peer; b0 += cap) {
+        const uint64_t piece = std::min<uint64_t>(cap, bytes_per_peer - b0);
+        uint64_t poff[RDC_MAX_RANKS] = {0}, plen[RDC_MAX_RANKS] = {0};
+        for (int p = 0; p < n_; ++p) {
+            poff[p] = off[p] + b0;
+            plen[p] = piece;
+        }
+        LaunchAlltoall(static_cast<const char*>(send), poff, plen, static_cast<char*>(recv), poff, plen, piece, stream);
+    }
+}
+
+void Communicator::LaunchAlltoall(const char* send, const uint64_t* send_off, const uint64_t* send_len, char* recv,
+                                  const uint64_t* recv_off, const uint64_t* recv_len, uint64_t equal_len,
+                                  hipStream_t stream) {
+    // the resident budget, equal on every rank; both roles wait, so each needs a block inside it
+    const int grid_cap = LaunchGrid(max_blocks(), occupancy_alltoall());
+    if (grid_cap < 2)
+        throw std::runtime_error("rdc: all-to-all needs 2 resident blocks per rank (RDC_NBLOCKS / ranks per GPU)");
+    const AlltoallPlan P = PlanAlltoall(n_, rank_, send_len, recv_len, layout(), cfg_.tile_bytes, grid_cap, equal_len);
+    CollArgs a;
+    FillArgsCommon(&a);
+    a.a2a_send = send;
+    uint64_t total = 0;
+    for (int p = 0; p < n_; ++p) {
+        a.a2a_soff[p] = send_off[p];
+        a.a2a_slen[p] = send_len[p];
+        a.cbuf[p] = recv;
+        a.off[p] = recv_off[p];
+        a.len[p] = recv_len[p];
+        a.tiles[p] = P.in_tiles[p];
+        total += send_len[p];
+    }
+    a.tile_bytes = P.tile_bytes;
+    a.nb_scatter = P.nb_push;
+    a.nb_gather = P.nb_land;
+    a.kind = RDC_KIND_ALLTOALL;
+    ++seq_;
+    const int grid = P.nb_push + P.nb_land;
+    last_launch_[0] = (uint64_t)grid;
+    last_launch_[1] = (uint64_t)P.nb_push;
+    last_launch_[2] = 0;
+    last_launch_[3] = (uint64_t)P.nb_land;
+    last_launch_[4] = P.tile_bytes;
+    last_launch_[5] = RDC_LAUNCH_ALLTOALL;
+    log_launch(this, seq_, RDC_LAUNCH_ALLTOALL, total, grid, P.tile_bytes);
+    hip_check(launch_alltoall(a, grid, stream), "launch all-to-all");
+}
+
 bool Communicator::SmallHostAllreduce(void* host, size_t count, int dtype, int op) {
     const size_t esz = rdc_dtype_size(dtype);
     const uint64_t bytes = (uint64_t)count * esz;
@@ -2929,7 +3022,8 @@ void Communicator::RaiseIfError(uint32_t e) const {
                                       "broadcast wait timed out", "ring step wait timed out",
                                       "allgather (buffers) wait timed out",
                                       "a peer's hand-off belongs to another communicator's collective",
-                                      "blocks of one launch read different launch numbers (RDC_SEQ_CHECK)"};
+                                      "blocks of one launch read different launch numbers (RDC_SEQ_CHECK)",
+                                      "all-to-all wait timed out"};
         if (e == RDC_KERR_ORDER)
             throw std::runtime_error(std::string("rdc: device collective failed on rank ") + std::to_string(rank_) +
                                      ": " + names[e] +
@@ -3038,7 +3132,7 @@ void Communicator::RaiseIfError(uint32_t e) const {
             (void)hipGetLastError();
         }
         throw std::runtime_error(std::string("rdc: device collective failed on rank ") + std::to_string(rank_) +
-                                 ": " + (e < 8 ? names[e] : "unknown") +
+                                 ": " + (e < 9 ? names[e] : "unknown") +
                                  " (a peer did not join the collective; communicator is now unusable; this "
                                  "rank's last launch: " + (al < 6 ? algos[al] : "?") + ", grid " +
                                  std::to_string(last_launch_[0]) + ", tile " + std::to_string(last_launch_[4]) +

@@ -250,6 +250,24 @@ public:
     void Broadcast(void* buf, size_t bytes, int root, hipStream_t stream);
     // bufs[c] (device) holds sizes[c] bytes; bufs[rank] is this rank's data
     void Allgather(void* const* bufs, const uint64_t* sizes, hipStream_t stream);
+    // Out-of-place all-to-all, stream-ordered (k_alltoall): bytes [send_off[p],
+    // +send_len[p]) of `send` land at [recv_off[r], +recv_len[r]) of rank p's
+    // `recv` (r = this rank); send_len[p] here = recv_len[r] there (the
+    // caller's contract, as in MPI: a receiver expecting more tiles than were
+    // sent ends in the bounded-wait error, any other mismatch lands undefined
+    // bytes inside that receive segment unreported).  Exactly ONE launch per call, all lengths zero included; a
+    // segment is at most AlltoallCap() bytes.  Refused before anything is
+    // launched (std::invalid_argument, rdc_plan.h CheckAlltoallv): a null
+    // buffer with bytes to move, own-segment lengths that differ, a segment
+    // beyond the capacity, receive segments that overlap, send and receive
+    // ranges that overlap.
+    void Alltoallv(const void* send, const uint64_t* send_off, const uint64_t* send_len, void* recv,
+                   const uint64_t* recv_off, const uint64_t* recv_len, hipStream_t stream);
+    // the equal split: segment p at p * bytes_per_peer on both sides, any size
+    // (ceil(bytes_per_peer / AlltoallCap()) launches, none for 0 bytes)
+    void Alltoall(const void* send, void* recv, uint64_t bytes_per_peer, hipStream_t stream);
+    // largest segment one all-to-all launch carries (world size 1: of MakeLayout(1, scratch))
+    uint64_t AlltoallCap() const;
     // waits for `stream`, then reads the device error word; throws on error
     void Check(hipStream_t stream);
     // split form of Check: after the caller synchronised the stream of its
@@ -428,6 +446,10 @@ private:
     // the scratch schedule of a reduce-scatter (k_rscatter) over chunk byte ranges of buf
     void LaunchReduceScatter(const KernelSet& ks, char* buf, const uint64_t* off, const uint64_t* len, uint64_t total,
                              size_t esz, hipStream_t stream);
+    // one all-to-all launch over validated segments; equal_len: the equal split's bytes per peer
+    // of this launch (PlanAlltoall's tile rule), 0 for alltoallv
+    void LaunchAlltoall(const char* send, const uint64_t* send_off, const uint64_t* send_len, char* recv,
+                        const uint64_t* recv_off, const uint64_t* recv_len, uint64_t equal_len, hipStream_t stream);
     void TuneBuffer(size_t bytes);
     // fresh: the allocations exported in this call, as (index in me.alloc,
     // the canary: the first bytes of one of this call's buffers)

@@ -41,10 +41,16 @@ enum {
 // RDC_KIND_TREE only names the kernel in occupancy queries; so does
 // RDC_KIND_RSCATTER_DIRECT: a reduce-scatter between registered buffers is a
 // launch of kind RDC_KIND_DIRECT.  RDC_KIND_RSCATTER: the mesh reduce-scatter,
-// whose launches end only after every peer's done word arrived)
+// whose launches end only after every peer's done word arrived.
+// RDC_KIND_ALLTOALL: the personalised exchange (k_alltoall), the allgather's
+// slot protocol with a different segment per destination)
 enum { RDC_KIND_NONE = 0, RDC_KIND_MESH = 1, RDC_KIND_RING = 2, RDC_KIND_BCAST = 3, RDC_KIND_ALLGATHER = 4,
        RDC_KIND_ONESHOT = 5, RDC_KIND_TREE = 6, RDC_KIND_DIRECT = 7, RDC_KIND_RSCATTER = 8,
-       RDC_KIND_RSCATTER_DIRECT = 9 };
+       RDC_KIND_RSCATTER_DIRECT = 9, RDC_KIND_ALLTOALL = 10 };
+// RdcCommLastLaunch's algo word (and the RDC_LAUNCH_LOG kind) of an all-to-all
+// launch: not an allreduce schedule, so outside RDC_ALGO_* (broadcast logs 100,
+// allgather 101)
+#define RDC_LAUNCH_ALLTOALL 102
 
 #define RDC_MAX_RANKS 16
 // 64-bit words from one hand-off flag to the next: 1 = packed (the default);
@@ -70,7 +76,8 @@ enum {
     // share a channel in different orders (rdc_device.h kTagBits)
     RDC_KERR_ORDER = 6,
     // RDC_SEQ_CHECK: two blocks of one launch read different launch numbers
-    RDC_KERR_SEQ = 7
+    RDC_KERR_SEQ = 7,
+    RDC_KERR_TIMEOUT_ALLTOALL = 8
 };
 
 static inline size_t rdc_dtype_size(int dtype) {
@@ -89,7 +96,7 @@ static inline int rdc_dtype_is_float(int dtype) {
 }
 
 // Everything one collective launch needs.  Passed by value as the kernel
-// argument (< 1.5 KiB).  Peer pointers are IPC-mapped (multi-process) or
+// argument (< 2 KiB).  Peer pointers are IPC-mapped (multi-process) or
 // direct (single-process); index [rank] is the local one.
 struct CollArgs {
     char* user;                          // local in-place buffer (byte 0 of the whole buffer)
@@ -146,6 +153,11 @@ struct CollArgs {
                                          //   finished reading with 0xFF (rdc_device.h block_poison)
     uint64_t* tlog;                      // RDC_LAUNCH_TIMES (debug): per launch {seq, block 0 start, latest block
                                          //   start, last block end} (wall_clock64) in a ring of 64 entries
+    // all-to-all (k_alltoall) only; appended so that no other kernel's argument offsets move.  The
+    // receive side uses cbuf / off / len / tiles per SOURCE rank c (cbuf[c] = the receive buffer)
+    const char* a2a_send;                // local send buffer (byte 0)
+    uint64_t a2a_soff[RDC_MAX_RANKS];    // byte offset in a2a_send of the segment for rank p
+    uint64_t a2a_slen[RDC_MAX_RANKS];    // its byte length (= len[rank] on rank p: the caller's contract)
 };
 
 // ------------------------------------------------ small-allreduce service --

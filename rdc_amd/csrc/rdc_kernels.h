@@ -26,11 +26,14 @@ struct KernelSet {
 
 // false if (dtype, op) is not a valid reference combination
 bool get_kernels(int dtype, int op, KernelSet* ks);
-// resident blocks per CU of k_bcast / k_allgather
+// resident blocks per CU of k_bcast / k_allgather / k_alltoall
 int occupancy_bcast();
 int occupancy_allgather();
+int occupancy_alltoall();
 hipError_t launch_bcast(const CollArgs& a, int grid, hipStream_t s);
 hipError_t launch_allgather(const CollArgs& a, int grid, hipStream_t s);
+// all-to-all: nb_scatter push blocks + nb_gather land blocks (rdc_plan.h PlanAlltoall)
+hipError_t launch_alltoall(const CollArgs& a, int grid, hipStream_t s);
 // coalesced allreduce: units[i].buf = user address; unpack = image -> buffers
 hipError_t launch_pack(const PackUnit* units, int nunits, char* image, int unpack, int grid, hipStream_t s);
 // plain device copy (dst may be IPC-mapped peer memory); never waits.

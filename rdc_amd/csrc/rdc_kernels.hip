@@ -70,6 +70,89 @@ __global__ __launch_bounds__(kBlock) void k_allgather(CollArgs a) {
     launch_done(a, seq);
 }
 
+// ============================================================ all-to-all ===
+// Personalised exchange (MI355X addition: the reference has no all-to-all).
+// Segment p of rank r's send buffer lands in segment r of rank p's receive
+// buffer.  The allgather's protocol with a source per destination: push blocks
+// copy tile t of send segment p into PEER p's AG slot `rank` and publish flag
+// (row n+rank, t) there; land blocks wait on their own flag (row n+c, t) and
+// copy the tile out of their own AG slot c into receive segment c.  One writer
+// per slot and per flag, no reduction.  Receivers never answer, so pushes wait
+// for the targets' done words of the previous launch, as in allgather_body.
+// The image of a segment starts at the slot's base (the receiver cannot know
+// the sender's address alignment): a side whose segment address is 16-B
+// aligned runs block_copy's 16-B path, any other its word paths.
+// Sender and receiver cut pair (r -> p) alike: ceil(len / tile_bytes) from the
+// one length both know (a2a_slen[p] here = len[r] there), tile_bytes equal on
+// every rank (rdc_plan.h PlanAlltoall).  The land items include this rank's
+// own segment (len[rank] = a2a_slen[rank]), copied local to local.
+__device__ void alltoall_body(const CollArgs& a, uint64_t seq) {
+    const int n = a.n, r = a.rank;
+    Abort ab{a.err, wall_clock64() + a.timeout_ticks, a.poll_rmw};
+    __shared__ uint64_t* s_flags[RDC_MAX_RANKS];
+    int b = blockIdx.x;
+    if (b < a.nb_scatter) {
+        int tmax = 0;  // outgoing tiles of the longest segment
+        for (int p = 0; p < n; ++p) {
+            const int tp = p == r ? 0 : (int)((a.a2a_slen[p] + a.tile_bytes - 1) / a.tile_bytes);
+            tmax = tp > tmax ? tp : tmax;
+        }
+        const int items = (n - 1) * tmax;
+        // Every push block with an item gates on the targets' done words of the
+        // previous launch before it writes their slots.  Block 0 gates even
+        // when this rank sends nothing (a zero row, an all-zero call): this
+        // launch then still ends only after every peer's previous launch did,
+        // which is the ordering a later launch relies on when it looks at the
+        // recorded kind of ITS predecessor — this launch — and finds no
+        // one-shot there.
+        if (b == 0 || b < items) {
+            if (threadIdx.x < (unsigned)(n - 1)) s_flags[threadIdx.x] = done_word(a, r, (r + 1 + threadIdx.x) % n);
+            __syncthreads();
+            if (!block_wait(s_flags, n - 1, seq_prev(seq), ab, RDC_KERR_TIMEOUT_ALLTOALL, a.uc, false)) return;
+        }
+        for (int it = b; it < items; it += a.nb_scatter) {
+            const int t = it / (n - 1);
+            const int p = (r + 1 + it % (n - 1)) % n;
+            const uint64_t toff = (uint64_t)t * a.tile_bytes;
+            if (toff >= a.a2a_slen[p]) continue;
+            uint64_t tlen = a.a2a_slen[p] - toff;
+            if (tlen > a.tile_bytes) tlen = a.tile_bytes;
+            block_copy<kDstPeer>(a.ag[p] + (uint64_t)r * a.slot_bytes + toff, a.a2a_send + a.a2a_soff[p] + toff, tlen);
+            block_publish1(flag_word(a, p, (uint64_t)(n + r) * a.max_tiles + t), seq, a.uc);
+        }
+        return;
+    }
+    b -= a.nb_scatter;
+    int tmax = 0;
+    for (int c = 0; c < n; ++c) tmax = a.tiles[c] > tmax ? a.tiles[c] : tmax;
+    const int items = n * tmax;  // source c = r: this rank's own segment, tiled like the others
+    for (int it = b; it < items; it += a.nb_gather) {
+        const int t = it / n;
+        const int c = (r + it % n) % n;
+        if (t >= a.tiles[c]) continue;
+        const uint64_t toff = (uint64_t)t * a.tile_bytes;
+        uint64_t tlen = a.len[c] - toff;
+        if (tlen > a.tile_bytes) tlen = a.tile_bytes;
+        if (c == r) {  // never leaves this rank: local to local, nothing to wait for
+            block_copy<kDstLocal>(a.cbuf[r] + a.off[r] + toff, a.a2a_send + a.a2a_soff[r] + toff, tlen);
+            continue;
+        }
+        if (threadIdx.x == 0) s_flags[0] = flag_word(a, r, (uint64_t)(n + c) * a.max_tiles + t);
+        __syncthreads();
+        if (!block_wait(s_flags, 1, seq, ab, RDC_KERR_TIMEOUT_ALLTOALL, a.uc)) return;
+        char* land = a.ag[r] + (uint64_t)c * a.slot_bytes + toff;
+        block_copy_pull(a.cbuf[c] + a.off[c] + toff, land, tlen);
+        __syncthreads();
+        if (a.poison) block_poison(land, tlen);  // writers gate on this rank's done word
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_alltoall(CollArgs a) {
+    uint64_t seq;
+    if (!launch_begin(a, &seq)) alltoall_body(a, seq);
+    launch_done(a, seq);
+}
+
 // ============================================================ pack ===
 // Coalesced allreduce (rdc_plan.h PlanCoalesced): copy every unit between its
 // user buffer and the chunk-major staging image.  Unit table in device memory
@@ -194,6 +277,16 @@ int occupancy_allgather() {
 
 hipError_t launch_allgather(const CollArgs& a, int grid, hipStream_t s) {
     hipLaunchKernelGGL(k_allgather, dim3(grid), dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+int occupancy_alltoall() {
+    static int c = 0;
+    return occupancy_of(k_alltoall, &c);
+}
+
+hipError_t launch_alltoall(const CollArgs& a, int grid, hipStream_t s) {
+    hipLaunchKernelGGL(k_alltoall, dim3(grid), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

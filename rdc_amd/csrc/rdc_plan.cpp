@@ -272,6 +272,64 @@ std::vector<Piece> PlanAllgather(int n, const uint64_t* sizes, const Layout& L, 
     return out;
 }
 
+uint64_t AlltoallCap(const Layout& L) { return round_down(L.slot_bytes - RDC_SLOT_ALIGN, RDC_SLOT_ALIGN); }
+
+AlltoallPlan PlanAlltoall(int n, int rank, const uint64_t* send_len, const uint64_t* recv_len, const Layout& L,
+                          size_t cfg_tile, int max_blocks, uint64_t equal_len) {
+    AlltoallPlan P;
+    memset(&P, 0, sizeof(P));
+    (void)L;  // the capacity check is the caller's (Communicator::Alltoallv refuses before launch)
+    const int G = std::max(2, max_blocks);
+    size_t t = cfg_tile;
+    if (t == 0) {
+        t = kAlltoallvTile;
+        if (equal_len)  // one push item per push block
+            t = std::min<size_t>(std::max<size_t>(equal_len * (uint64_t)std::max(1, n - 1) / (size_t)(G / 2), t),
+                                 (size_t)1 << 20);
+    }
+    t = std::max<size_t>(round_up(t, RDC_SLOT_ALIGN), RDC_MIN_TILE);
+    P.tile_bytes = t;
+    int To = 0, Ti = 0;
+    for (int p = 0; p < n; ++p) {
+        P.out_tiles[p] = p == rank ? 0 : (int)((send_len[p] + t - 1) / t);
+        P.in_tiles[p] = (int)((recv_len[p] + t - 1) / t);
+        To = std::max(To, P.out_tiles[p]);
+        Ti = std::max(Ti, P.in_tiles[p]);
+    }
+    P.nb_push = std::max(1, std::min((n - 1) * To, G / 2));
+    P.nb_land = std::max(1, std::min(n * Ti, G - G / 2));
+    return P;
+}
+
+const char* CheckAlltoallv(int n, int rank, const void* send, const uint64_t* send_off, const uint64_t* send_len,
+                           const void* recv, const uint64_t* recv_off, const uint64_t* recv_len, uint64_t cap) {
+    if (!send_off || !send_len || !recv_off || !recv_len) return "rdc: all-to-all: null offset or length array";
+    uint64_t slo = ~(uint64_t)0, shi = 0, rlo = ~(uint64_t)0, rhi = 0;  // hulls, as addresses
+    for (int p = 0; p < n; ++p) {
+        if (send_len[p] && !send) return "rdc: all-to-all: null send buffer with bytes to send";
+        if (recv_len[p] && !recv) return "rdc: all-to-all: null receive buffer with bytes to receive";
+        if (cap && (send_len[p] > cap || recv_len[p] > cap))
+            return "rdc: all-to-all: a segment is longer than one launch carries (RdcPlanAlltoallCap); slice the "
+                   "exchange";
+        if (send_len[p]) {
+            slo = std::min<uint64_t>(slo, (uint64_t)(uintptr_t)send + send_off[p]);
+            shi = std::max<uint64_t>(shi, (uint64_t)(uintptr_t)send + send_off[p] + send_len[p]);
+        }
+        if (recv_len[p]) {
+            rlo = std::min<uint64_t>(rlo, (uint64_t)(uintptr_t)recv + recv_off[p]);
+            rhi = std::max<uint64_t>(rhi, (uint64_t)(uintptr_t)recv + recv_off[p] + recv_len[p]);
+        }
+        for (int q = 0; q < p; ++q)
+            if (recv_len[p] && recv_len[q] && recv_off[p] < recv_off[q] + recv_len[q] &&
+                recv_off[q] < recv_off[p] + recv_len[p])
+                return "rdc: all-to-all: receive segments overlap each other";
+    }
+    if (send_len[rank] != recv_len[rank]) return "rdc: all-to-all: this rank's own segment has two lengths";
+    if (slo < shi && rlo < rhi && slo < rhi && rlo < shi)
+        return "rdc: all-to-all: send and receive ranges overlap (the exchange is out of place)";
+    return "";
+}
+
 std::vector<Piece> PlanBroadcast(uint64_t bytes, const Layout& L, size_t cfg_tile, int max_blocks) {
     std::vector<Piece> out;
     const size_t cap = round_down(L.region_bytes - RDC_SLOT_ALIGN, RDC_SLOT_ALIGN);
@@ -537,6 +595,31 @@ HbmBytes ModelReduceScatterBytes(int n, uint64_t count, size_t esz, int algo) {
         h.write_sum += wr;
         h.egress_max = std::max(h.egress_max, eg);
     }
+    return h;
+}
+
+// One all-to-all on rank `rank`, in ModelHbmBytes' conventions (a remote access
+// counted at the rank that issues it), per the loops of k_alltoall:
+//   push: load every segment for a peer from the send buffer, store it into
+//         that peer's AG slot (remote: egress)
+//   land: load every peer's segment from this rank's own AG slots, store it
+//         into the receive buffer
+//   own:  load the own segment from the send buffer, store it into the
+//         receive buffer (no scratch)
+HbmBytes ModelAlltoallBytes(int n, int rank, const uint64_t* send_len, const uint64_t* recv_len) {
+    HbmBytes h;
+    uint64_t send_all = 0, send_peers = 0, recv_all = 0, recv_peers = 0;
+    for (int p = 0; p < n; ++p) {
+        send_all += send_len[p];
+        recv_all += recv_len[p];
+        if (p != rank) {
+            send_peers += send_len[p];
+            recv_peers += recv_len[p];
+        }
+    }
+    h.read_max = h.read_sum = send_all + recv_peers;
+    h.write_max = h.write_sum = send_peers + recv_all;
+    h.egress_max = send_peers;
     return h;
 }
 

@@ -119,6 +119,45 @@ Piece PlanOneshot(int n, uint64_t count, size_t esz, const Layout& L, size_t cfg
 // blocks, nb_gather = gather blocks).
 std::vector<Piece> PlanAllgather(int n, const uint64_t* sizes, const Layout& L, size_t cfg_tile, int max_blocks);
 
+// ---------------------------------------------------------- all-to-all ---
+// Personalised exchange (k_alltoall): segment p of rank r's send buffer lands
+// in segment r of rank p's receive buffer, through peer p's AG slot r.
+// Launch numbers are global and a rank knows only its row (send_len) and
+// column (recv_len) of the size matrix, so sender and receiver must cut pair
+// (r -> p) alike from what both know:
+//   * one launch per plan; a segment is at most AlltoallCap(L) bytes;
+//   * tile_bytes depends only on values equal on every rank: cfg_tile, else
+//     kAlltoallvTile (alltoallv), else — the equal-split form, equal_len =
+//     this launch's bytes per peer, known everywhere — one push item per push
+//     block, within [kAlltoallvTile, 1 MiB];
+//   * tiles of a pair = ceil(len / tile_bytes), from the one length both ends
+//     have (send_len[p] on r = recv_len[r] on p: the caller's contract).
+// A plan whose lengths are all zero is still one launch (both roles hold one
+// block): the call is collective and consumes its launch number.
+// max_blocks is the resident budget of the launch (LaunchGrid) and must be at
+// least 2: each role needs a block, so a budget of 1 would be exceeded (the
+// plan then still holds 1 + 1 blocks; Communicator::LaunchAlltoall refuses such
+// a budget, which no MI355X configuration produces).
+struct AlltoallPlan {
+    uint64_t tile_bytes;
+    int out_tiles[RDC_MAX_RANKS];  // tiles of the segment for rank p ([rank] = 0: it never leaves)
+    int in_tiles[RDC_MAX_RANKS];   // tiles of the segment from rank c ([rank]: the own segment's local copy)
+    int nb_push, nb_land;          // push blocks (items (peer, tile)), land blocks (items (source, tile))
+};
+constexpr uint64_t kAlltoallvTile = (uint64_t)64 << 10;
+// largest segment one launch carries: the allgather's per-piece capacity
+uint64_t AlltoallCap(const Layout& L);
+AlltoallPlan PlanAlltoall(int n, int rank, const uint64_t* send_len, const uint64_t* recv_len, const Layout& L,
+                          size_t cfg_tile, int max_blocks, uint64_t equal_len = 0);
+// What one rank can check of an alltoallv call before launching; returns the
+// refusal ("" = fine): a null buffer with bytes to move, own-segment lengths
+// that differ, a segment longer than cap (cap = 0: not checked — the equal
+// split cuts its own pieces), receive segments that overlap each other, send
+// and receive ranges that overlap (each side's extent = the hull of its
+// non-empty segments).
+const char* CheckAlltoallv(int n, int rank, const void* send, const uint64_t* send_off, const uint64_t* send_len,
+                           const void* recv, const uint64_t* recv_off, const uint64_t* recv_len, uint64_t cap);
+
 // Broadcast pieces of `bytes` (use off/len/mis/tiles [0]).
 std::vector<Piece> PlanBroadcast(uint64_t bytes, const Layout& L, size_t cfg_tile, int max_blocks);
 
@@ -210,5 +249,10 @@ struct HbmBytes {
 HbmBytes ModelHbmBytes(int n, uint64_t count, size_t esz, int algo);
 // The same model of one reduce-scatter (algo RDC_ALGO_MESH or RDC_ALGO_DIRECT)
 HbmBytes ModelReduceScatterBytes(int n, uint64_t count, size_t esz, int algo);
+// The same model of one all-to-all on rank `rank` (one rank's row send_len and
+// column recv_len of the size matrix, so max = sum = this rank's bytes):
+// reads = the send buffer + this rank's own slots, writes = the peers' slots
+// (remote, counted here: egress) + the receive buffer
+HbmBytes ModelAlltoallBytes(int n, int rank, const uint64_t* send_len, const uint64_t* recv_len);
 
 }  // namespace rdc_amd

@@ -14,6 +14,16 @@ direct schedules as the yardstick (allreduce_mesh, allreduce_direct); next to
 the direct entry, rs_direct_hbm_fraction = the modelled HBM bytes (read + write,
 the most of any rank) of the direct reduce-scatter over the direct allreduce's
 (RdcPlanReduceScatterBytes / RdcPlanHbmBytes).
+SWEEP_COLLECTIVE=alltoall times RdcCommAlltoall (sizes are MiB per PAIR) and the
+same exchange written with Comm.isend / Comm.irecv on the same buffers, in
+alternating rounds (SWEEP_ROUNDS, default 5): per form the median over rounds of
+the slowest rank's time per call and the spread (max - min) / median.  The
+collective is timed twice: "alltoall" = calls enqueued back to back, one
+synchronise at the end (pipelined throughput per call), "alltoall_sync" = a
+synchronise after every call, which is what the point-to-point form does (its
+waits complete every call); "speedup" compares the two synchronised forms.  Next to
+them the all-to-all's share of the HBM peak by RdcPlanAlltoallBytes (every
+rank's bytes: the ranks share one GPU).
 
     python -m torch.distributed.run --nproc-per-node N tools/algo_sweep.py [sizes_MiB] [steps]
 """
@@ -25,6 +35,89 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+HBM_PEAK = 8.0e12  # bytes / s, one MI355X
+
+
+def alltoall_sweep(sizes, steps, rank, world, comm, sp):
+    """sizes: MiB per PAIR.  Per size, `rounds` rounds alternating the two forms
+    on the same buffers; a round's time is the slowest rank's, the figure the
+    median over rounds, the spread (max - min) / median."""
+    import torch
+    import torch.distributed as dist
+    from rdc_amd._lib import _LIB, check_call
+    rounds = int(os.environ.get("SWEEP_ROUNDS", "5"))
+    big = int(max(sizes) * (1 << 20))
+    send = torch.empty(world * big, dtype=torch.uint8, device="cuda")
+    recv = torch.empty(world * big, dtype=torch.uint8, device="cuda")
+    check_call(_LIB.RdcFill(ctypes.c_void_p(send.data_ptr()), world * big, 1, 0x5EED0000, rank, sp))
+    out = {}
+    for mib in sizes:
+        nb = int(mib * (1 << 20))
+
+        def a2a():
+            check_call(_LIB.RdcCommAlltoall(comm.handle, ctypes.c_void_p(send.data_ptr()),
+                                            ctypes.c_void_p(recv.data_ptr()), nb, sp))
+
+        def p2p():  # the same exchange as a user of the parent commit writes it
+            wcs = []
+            for k in range(1, world):
+                src, dst = (rank - k) % world, (rank + k) % world
+                wcs.append(comm.irecv(recv[src * nb: (src + 1) * nb], src))
+                wcs.append(comm.isend(send[dst * nb: (dst + 1) * nb], dst))
+            recv[rank * nb: (rank + 1) * nb].copy_(send[rank * nb: (rank + 1) * nb])
+            for w in wcs:
+                w.wait()
+
+        def timed(fn, n_steps):
+            torch.cuda.synchronize()
+            dist.barrier()
+            t0 = time.perf_counter()
+            for _ in range(n_steps):
+                fn()
+            torch.cuda.synchronize()
+            t = torch.tensor([(time.perf_counter() - t0) / n_steps], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            return float(t[0])
+
+        def a2a_sync():  # one call at a time, as the point-to-point form completes every call
+            a2a()
+            torch.cuda.synchronize()
+
+        n_a2a = max(steps, min(500, int(2e8 // max(nb * (world - 1), 1))))
+        n_p2p = max(3, min(steps, int(5e7 // max(nb * (world - 1), 1))))
+        for _ in range(3):
+            a2a()
+        p2p()
+        comm.check(sp)
+        ta, tsy, tp = [], [], []
+        for _ in range(rounds):
+            ta.append(timed(a2a, n_a2a))
+            tsy.append(timed(a2a_sync, min(n_a2a, 100)))
+            tp.append(timed(p2p, n_p2p))
+        comm.check(sp)
+        row = {}
+        for name, ts in (("alltoall", ta), ("alltoall_sync", tsy), ("isend_irecv", tp)):
+            ts.sort()
+            med = ts[len(ts) // 2]
+            row[name] = round(med * 1e3, 4)
+            row[name + "_spread"] = round((ts[-1] - ts[0]) / med, 3)
+        m = (ctypes.c_uint64 * 5)()
+        lens = (ctypes.c_uint64 * 16)(*([nb] * world))
+        check_call(_LIB.RdcPlanAlltoallBytes(world, rank, lens, lens, m))
+        # every rank's modelled bytes share this GPU's HBM
+        row["alltoall_hbm_fraction"] = round(world * (m[0] + m[1]) / (row["alltoall"] * 1e-3) / HBM_PEAK, 4)
+        # like with like: both forms completing every call
+        row["speedup"] = round(row["isend_irecv"] / row["alltoall_sync"], 2)
+        ll = (ctypes.c_uint64 * 6)()
+        check_call(_LIB.RdcCommLastLaunch(comm.handle, ll))
+        row["grid_push_land_tile"] = [int(ll[0]), int(ll[1]), int(ll[3]), int(ll[4])]
+        out["%g MiB" % mib] = row
+    if rank == 0:
+        print(json.dumps({"algo_sweep_ms_per_call": out, "world": world, "collective": "alltoall",
+                          "size_is": "MiB per pair", "rounds": rounds, "ranks_share_gpu": True,
+                          "hbm_peak_bytes_per_s": HBM_PEAK}), flush=True)
 
 
 def main():
@@ -40,6 +133,11 @@ def main():
     rdc_amd.init([])
     comm = rdc_amd.get_comm("main")
     sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if os.environ.get("SWEEP_COLLECTIVE", "allreduce") == "alltoall":
+        alltoall_sweep(sizes, steps, rank, world, comm, sp)
+        dist.barrier()
+        rdc_amd.finalize()
+        return
     half = ctypes.c_uint64()
     check_call(_LIB.RdcCommGetParam(comm.handle, b"slot_bytes", ctypes.byref(half)))
     big = int(max(sizes) * (1 << 20))
