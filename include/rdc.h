@@ -333,6 +333,13 @@ public:
     virtual void ReduceScatter(void* sendrecvbuf, uint64_t count, mpi::DataType dtype, mpi::OpType op) {
         detail::Check(RdcReduceScatterOn(handle_, sendrecvbuf, count, (int)dtype, (int)op), "ReduceScatter");
     }
+    /*! \brief in-place reduction of count elements to rank root (host or device
+     *  memory; MPI_Reduce): on root sendrecvbuf receives the reduction, with
+     *  Allreduce's bits (the ring order at every size); on every other rank it
+     *  is only read.  root must be the same on every rank */
+    virtual void ReduceTo(void* sendrecvbuf, uint64_t count, mpi::DataType dtype, mpi::OpType op, int root) {
+        detail::Check(RdcReduceToOn(handle_, sendrecvbuf, count, (int)dtype, (int)op, root), "ReduceTo");
+    }
     /*! \brief allreduce with a custom HOST reducer (communicator.h:92-93, virtual
      *  here).  sendrecvbuf needs an item size (Count()).  Ring order per Split
      *  chunk above rdc_reduce_ring_mincount bytes, the tree's order at or below
@@ -651,6 +658,19 @@ inline std::pair<uint64_t, uint64_t> ReduceScatter(DType* sendrecvbuf, uint64_t 
     uint64_t lo = 0, hi = 0;
     detail::Check(RdcPlanSplit(count, c->GetWorldSize(), c->GetRank(), &lo, &hi), "ReduceScatter");
     return std::pair<uint64_t, uint64_t>(lo, hi);
+}
+
+/*! \brief in-place reduction to rank root (MI355X addition to the public
+ *  surface; MPI_Reduce.  rdc::Reduce names nothing here, but the C ABI's
+ *  RdcReduce is the local element-wise reduce, hence ReduceTo).  On root all
+ *  count elements of sendrecvbuf receive the reduction, with the bits
+ *  Allreduce<OP, DType> puts there by the ring order, at every size; on every
+ *  other rank sendrecvbuf stays exactly as passed.  root must be the same on
+ *  every rank; a root outside [0, GetWorldSize()) fails before anything is
+ *  launched */
+template <typename OP, typename DType>
+inline void ReduceTo(DType* sendrecvbuf, uint64_t count, int root, const std::string& comm_name = kMainCommName) {
+    GetCommunicator(comm_name)->ReduceTo(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType, root);
 }
 
 /*! \brief out-of-place all-to-all, equal split (MI355X addition to the public

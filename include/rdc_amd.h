@@ -104,6 +104,25 @@ int RdcAllgatherOn(void* comm, void** bufs, const size_t* sizes);
 int RdcReduceScatter(void* sendrecv, size_t count, int dtype, int op);
 int RdcReduceScatterOn(void* comm, void* sendrecv, size_t count, int dtype, int op);
 
+/* In-place reduction to one rank (MPI_Reduce, ncclReduce; named ReduceTo
+ * because RdcReduce is the local element-wise reduce).  On rank `root` all
+ * count elements of sendrecv receive the reduction over all ranks,
+ * bit-identical to what RdcAllreduce leaves there by the ring order: element e
+ * of chunk c = utils::Split(0, count, n)[c] is x[c] (+) (x[c+1] (+) ... (+)
+ * x[c-1]).  The ring order applies at EVERY size: rdc_reduce_ring_mincount is
+ * not consulted.  On every other rank sendrecv is only read: every byte stays
+ * exactly as the caller passed it.  `root` must be the same on every rank (the
+ * caller's contract, as for RdcBroadcast).  The (dtype, op) pairs are the
+ * allreduce's.  Refused with a message in RdcGetLastError before anything is
+ * launched: a root outside [0, n), an unsupported (dtype, op), a buffer not
+ * aligned to its element size, a null buffer with count > 0.  count = 0 or
+ * world size 1 succeed without touching the GPU.  Host or device memory
+ * (detected); synchronous.  A host buffer goes up whole on every rank and the
+ * whole result is copied back on the root only: a non-root host buffer is
+ * never written.  RdcReduceTo uses the "main" communicator. */
+int RdcReduceTo(void* sendrecv, size_t count, int dtype, int op, int root);
+int RdcReduceToOn(void* comm, void* sendrecv, size_t count, int dtype, int op, int root);
+
 /* All-to-all, out of place (MI355X addition: the reference has no personalised
  * exchange; its custom-reducer allreduce builds one out of ISend / IRecv).
  * On rank r, bytes [send_off[p], send_off[p] + send_len[p]) of `send` land at
@@ -271,6 +290,19 @@ int RdcCommAllreduceCoalesced(void* comm, void* const* dev_bufs, const size_t* c
 int RdcCommBroadcast(void* comm, void* dev_buf, size_t bytes, int root, void* stream);
 /* device-resident allgather of per-rank buffers (see RdcAllgather), stream-ordered */
 int RdcCommAllgather(void* comm, void** dev_bufs, const size_t* sizes, void* stream);
+/* Device-resident in-place reduction to `root` (see RdcReduceTo for the result
+ * and the refusals), stream-ordered; errors raised inside the kernel surface
+ * at RdcCommCheck.  One schedule, on the scratch path: the mesh allreduce with
+ * its second half narrowed to one destination — every rank pushes the other
+ * chunks to their owners, owner r folds chunk r in its ring order, the root
+ * into its own buffer and every other owner into the root's scratch only,
+ * which the root copies into its buffer.  Works in single-process groups and
+ * can be captured in a hipGraph.  A launch ends only after every peer's launch
+ * ended, so the scratch slots need no gate in whatever launch follows.
+ * RdcCommTune / RDC_NBLOCKS / RDC_TILE_BYTES apply as for a mesh allreduce of
+ * the same bytes.  RdcCommLastLaunch reports algo 2, and gather blocks on the
+ * root only. */
+int RdcCommReduceTo(void* comm, void* dev_buf, size_t count, int dtype, int op, int root, void* stream);
 /* Device-resident all-to-all (see RdcAlltoall / RdcAlltoallv for the result,
  * the contract and the refusals), stream-ordered; the scratch path (k_alltoall:
  * every rank pushes segment p into peer p's allgather slot `rank` and lands its
@@ -511,6 +543,23 @@ int RdcPlanReduceScatter(int n, size_t count, int dtype, size_t scratch_bytes, s
  * link, chunk r stored once).  out5 as RdcPlanHbmBytes; egress = the bytes of
  * this rank's buffer that go to peers (pushed by it, or loaded by them). */
 int RdcPlanReduceScatterBytes(int n, size_t count, int dtype, int algo, uint64_t* out5);
+
+/* The launches of a rooted reduce (RdcCommReduceTo) on rank `rank`, in
+ * RdcPlanAllreduce's records.  The offsets, lengths, mis, tiles and tile bytes
+ * are RdcPlanAllreduce(algo 2)'s for the same arguments and depend on neither
+ * rank nor root (both ends of every hand-off cut alike); the root gets the
+ * mesh's scatter / reduce / gather split, every other rank RdcPlanReduceScatter's
+ * (nb_gather = 0).  Refused: a rank or root outside [0, n), an unsupported
+ * (dtype, op). */
+int RdcPlanReduceTo(int n, int rank, int root, size_t count, int dtype, int op, size_t scratch_bytes,
+                    size_t tile_bytes, int max_blocks, uint64_t* out, int max_pieces, int* out_pieces);
+/* RdcPlanHbmBytes' model of one rooted reduce on rank `rank`: every rank loads
+ * the other chunks and stores them remotely, and loads n x its own chunk; a
+ * non-root rank stores the folded chunk remotely (both stores are egress); the
+ * root stores it locally, loads its AG slots and stores the gathered chunks.
+ * out5 as RdcPlanHbmBytes (for one rank max = sum); rank < 0: the maxima and
+ * sums over all n ranks. */
+int RdcPlanReduceToBytes(int n, int rank, int root, size_t count, int dtype, uint64_t* out5);
 
 /* The one launch of an all-to-all as rank `rank` plans it from its row
  * (send_len[n]) and column (recv_len[n]) of the size matrix.  out (36 words):

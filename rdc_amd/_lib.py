@@ -51,6 +51,11 @@ def _load():
         "RdcPlanSplit": (i, [sz, i, i, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "RdcPlanReduceScatter": (i, [i, sz, i, sz, sz, i, ctypes.POINTER(u64), i, ctypes.POINTER(ctypes.c_int)]),
         "RdcPlanReduceScatterBytes": (i, [i, sz, i, i, ctypes.POINTER(u64)]),
+        "RdcReduceTo": (i, [vp, sz, i, i, i]),
+        "RdcReduceToOn": (i, [vp, vp, sz, i, i, i]),
+        "RdcCommReduceTo": (i, [vp, vp, sz, i, i, i, vp]),
+        "RdcPlanReduceTo": (i, [i, i, i, sz, i, i, sz, sz, i, ctypes.POINTER(u64), i, ctypes.POINTER(ctypes.c_int)]),
+        "RdcPlanReduceToBytes": (i, [i, i, i, sz, i, ctypes.POINTER(u64)]),
         "RdcAlltoall": (i, [vp, vp, sz]),
         "RdcAlltoallOn": (i, [vp, vp, vp, sz]),
         "RdcAlltoallv": (i, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp, ctypes.POINTER(sz), ctypes.POINTER(sz)]),

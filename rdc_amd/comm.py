@@ -142,6 +142,23 @@ class Comm(object):
         lo, hi = split_range(tensor.numel(), self.world_size, self.rank)
         return tensor.view(-1)[lo:hi]
 
+    def reduce(self, tensor, op, root, stream=None):
+        """In-place reduction of a contiguous ROCm tensor to rank ``root``
+        (RdcCommReduceTo; MPI_Reduce): on ``root`` the tensor receives the
+        reduction, with the bits ``allreduce`` puts there by the ring order, at
+        every size; on every other rank it stays exactly as passed.  ``root``
+        must be the same on every rank.  Returns the tensor.  A contiguous
+        numpy array is reduced synchronously (RdcReduceToOn), in place
+        likewise; a non-root array is never written."""
+        from .core import host_reduce
+        if not _is_tensor(tensor):
+            return host_reduce(tensor, op, root, comm=self)
+        _dev._check_tensor(tensor)
+        s = stream if stream is not None else _dev.current_stream_ptr(tensor.device)
+        check_call(_LIB.RdcCommReduceTo(self.handle, ctypes.c_void_p(tensor.data_ptr()), tensor.numel(),
+                                        _dev.dtype_enum(tensor.dtype), int(op), int(root), s))
+        return tensor
+
     def allreduce_coalesced(self, tensors, op, algo="auto", stream=None):
         """Bucketed allreduce of a list of contiguous ROCm tensors of one dtype,
         in place: the result of ``allreduce`` on each tensor in order

@@ -271,6 +271,36 @@ def host_all_to_all_v(send, send_counts, recv, recv_counts, send_displs=None, re
     return recv
 
 
+def reduce(data, op, root):
+    """In-place reduction to rank ``root`` on the "main" communicator
+    (RdcReduceTo; MPI_Reduce): on ``root`` ``data`` receives the reduction —
+    the bits ``allreduce`` puts there by the ring order, at every size — and
+    on every other rank ``data`` stays exactly as passed.  ``root`` must be the
+    same on every rank.  A contiguous numpy.ndarray (synchronous) or a ROCm
+    torch.Tensor (stream-ordered on torch's current stream); returns ``data``."""
+    op = int(Op(op) if not isinstance(op, Op) else op)
+    if type(data).__module__.startswith("torch"):
+        from . import comm as _comm
+        return _comm.get_comm("main").reduce(data, op, root)
+    return host_reduce(data, op, root)
+
+
+def host_reduce(data, op, root, comm=None):
+    """reduce of a host ndarray: RdcReduceTo on "main", or RdcReduceToOn on the
+    Comm ``comm``."""
+    op = int(Op(op) if not isinstance(op, Op) else op)
+    if not isinstance(data, np.ndarray) or not data.flags.c_contiguous:
+        raise TypeError("reduce takes a contiguous numpy.ndarray or a torch.Tensor")
+    if data.dtype not in DTYPE_ENUM__:
+        raise TypeError("data type %s not supported" % str(data.dtype))
+    ptr = data.ctypes.data_as(ctypes.c_void_p)
+    if comm is not None:
+        check_call(_LIB.RdcReduceToOn(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], op, int(root)))
+    else:
+        check_call(_LIB.RdcReduceTo(ptr, data.size, DTYPE_ENUM__[data.dtype], op, int(root)))
+    return data
+
+
 def allreduce_coalesced(arrays, op):
     """Bucketed allreduce of a list of arrays of one dtype, in place: the
     result of ``allreduce`` on each one (bit-identical), moved in fused device

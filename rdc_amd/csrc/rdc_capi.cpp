@@ -396,6 +396,31 @@ void reduce_scatter_sync(Manager& m, Communicator* c, void* sendrecv, size_t cou
     c->Check(s);
 }
 
+// synchronous in-place reduction to `root` of host or device memory on communicator c
+void reduce_to_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, int dtype, int op, int root) {
+    check_dtype_op(dtype, op);
+    if (root < 0 || root >= c->size())
+        throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " +
+                                    std::to_string(c->size()) + ")");
+    if (c->size() == 1 || count == 0) return;
+    if (!sendrecv) throw std::invalid_argument("rdc: null buffer");
+    hipStream_t s = manager_stream(m, c->device());
+    if (is_device_pointer(sendrecv)) {
+        c->ReduceTo(sendrecv, count, dtype, op, root, s);
+        c->Check(s);
+        return;
+    }
+    // host buffer: the whole input up on every rank, the device reduce, the
+    // whole result back on the root only — a non-root host buffer is never written
+    const size_t esz = rdc_dtype_size(dtype);
+    if ((uintptr_t)sendrecv % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
+    char* d = static_cast<char*>(staging(m, std::max<size_t>(count * esz, 256), c->device()));
+    hcheck(hipMemcpyAsync(d, sendrecv, count * esz, hipMemcpyHostToDevice, s), "H2D");
+    c->ReduceTo(d, count, dtype, op, root, s);
+    if (c->rank() == root) hcheck(hipMemcpyAsync(sendrecv, d, count * esz, hipMemcpyDeviceToHost, s), "D2H");
+    c->Check(s);
+}
+
 // synchronous coalesced allreduce of host or device buffers (all of one kind)
 void allreduce_coalesced_sync(Manager& m, Communicator* c, void** bufs, const size_t* counts, int nbuf, int dtype,
                               int op) {
@@ -699,6 +724,31 @@ int RdcCommReduceScatter(void* comm, void* dev_buf, size_t count, int dtype, int
                                         " (0 auto, 2 mesh, 6 direct)");
         as_comm(comm)->ReduceScatter(dev_buf, count, dtype, op, static_cast<hipStream_t>(stream), algo);
     });
+}
+
+int RdcReduceTo(void* sendrecv, size_t count, int dtype, int op, int root) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] {
+        require_init(m);
+        check_dtype_op(dtype, op);
+        if (root < 0 || root >= m.world)
+            throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " +
+                                        std::to_string(m.world) + ")");
+        // world size 1: the buffer already holds its own reduction
+        if (m.world == 1 || count == 0) return;
+        reduce_to_sync(m, get_comm(m, "main", true), sendrecv, count, dtype, op, root);
+    });
+}
+
+int RdcReduceToOn(void* comm, void* sendrecv, size_t count, int dtype, int op, int root) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] { reduce_to_sync(m, as_comm(comm), sendrecv, count, dtype, op, root); });
+}
+
+int RdcCommReduceTo(void* comm, void* dev_buf, size_t count, int dtype, int op, int root, void* stream) {
+    return guard([&] { as_comm(comm)->ReduceTo(dev_buf, count, dtype, op, root, static_cast<hipStream_t>(stream)); });
 }
 
 int RdcAllreduceCoalesced(void** bufs, const size_t* counts, int nbuf, int dtype, int op) {
@@ -1014,6 +1064,53 @@ int RdcPlanReduceScatter(int n, size_t count, int dtype, size_t scratch_bytes, s
         const Layout L = MakeLayout(n, scratch_bytes ? scratch_bytes : CommConfig().scratch_bytes);
         const std::vector<Piece> plan =
             PlanReduceScatter(n, count, esz, L, tile_bytes, max_blocks > 0 ? max_blocks : 256);
+        *out_pieces = (int)plan.size();
+        for (int k = 0; k < (int)plan.size() && k < max_pieces && out; ++k) {
+            uint64_t* o = out + (size_t)k * RDC_PLAN_WORDS;
+            const Piece& p = plan[(size_t)k];
+            o[0] = p.tile_bytes;
+            o[1] = (uint64_t)p.nb_scatter;
+            o[2] = (uint64_t)p.nb_reduce;
+            o[3] = (uint64_t)p.nb_gather;
+            for (int c = 0; c < RDC_MAX_RANKS; ++c) {
+                o[4 + c] = p.off[c];
+                o[20 + c] = p.len[c];
+                o[36 + c] = p.mis[c];
+                o[52 + c] = (uint64_t)p.tiles[c];
+            }
+        }
+    });
+}
+
+int RdcPlanReduceToBytes(int n, int rank, int root, size_t count, int dtype, uint64_t* out5) {
+    return guard([&] {
+        const size_t esz = rdc_dtype_size(dtype);
+        if (n < 1 || n > RDC_MAX_RANKS || esz == 0 || !out5 || rank >= n) throw std::invalid_argument("rdc: bad argument");
+        if (root < 0 || root >= n)
+            throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " +
+                                        std::to_string(n) + ")");
+        const HbmBytes h = ModelReduceToBytes(n, rank, root, count, esz);
+        out5[0] = h.read_max;
+        out5[1] = h.write_max;
+        out5[2] = h.read_sum;
+        out5[3] = h.write_sum;
+        out5[4] = h.egress_max;
+    });
+}
+
+int RdcPlanReduceTo(int n, int rank, int root, size_t count, int dtype, int op, size_t scratch_bytes,
+                    size_t tile_bytes, int max_blocks, uint64_t* out, int max_pieces, int* out_pieces) {
+    return guard([&] {
+        check_dtype_op(dtype, op);
+        const size_t esz = rdc_dtype_size(dtype);
+        if (n < 1 || n > RDC_MAX_RANKS || rank < 0 || rank >= n || esz == 0 || !out_pieces)
+            throw std::invalid_argument("rdc: bad argument");
+        if (root < 0 || root >= n)
+            throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " +
+                                        std::to_string(n) + ")");
+        const Layout L = MakeLayout(n, scratch_bytes ? scratch_bytes : CommConfig().scratch_bytes);
+        const std::vector<Piece> plan =
+            PlanReduceTo(n, rank, root, count, esz, L, tile_bytes, max_blocks > 0 ? max_blocks : 256);
         *out_pieces = (int)plan.size();
         for (int k = 0; k < (int)plan.size() && k < max_pieces && out; ++k) {
             uint64_t* o = out + (size_t)k * RDC_PLAN_WORDS;

@@ -1326,6 +1326,38 @@ void Communicator::ReduceScatter(void* buf, size_t count, int dtype, int op, hip
     LaunchReduceScatter(ks, static_cast<char*>(buf), off, len, nb, esz, stream);
 }
 
+// The reduction to one rank (MPI_Reduce, ncclReduce), in place: on `root` all
+// count elements hold the bits Allreduce's ring order puts there — element e
+// of Split chunk c is x[c] (+) (x[c+1] (+) ... (+) x[c-1]) — and on every
+// other rank buf is only read.  The ring order holds at every size, as for the
+// reduce-scatter: cfg_.ring_mincount is not consulted.  One schedule, on the
+// scratch path (k_rooted): the mesh with its results going to the root only.
+// Everything is checked before the first launch; `root` must be the same on
+// every rank (the caller's contract, as for Broadcast).
+void Communicator::ReduceTo(void* buf, size_t count, int dtype, int op, int root, hipStream_t stream) {
+    KernelSet ks;
+    if (!get_kernels(dtype, op, &ks))
+        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
+                                    std::to_string(op) + ")");
+    if (root < 0 || root >= n_)
+        throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " + std::to_string(n_) +
+                                    ")");
+    const size_t esz = rdc_dtype_size(dtype);
+    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
+    if (n_ == 1 || count == 0) return;
+    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ChannelCall call(ch_.get(), stream);
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
+    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
+    for (int c = 0; c < n_; ++c) {
+        off[c] = (uint64_t)cb[c] * esz;
+        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
+    }
+    LaunchReduceTo(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, root, stream);
+}
+
 // ------------------------------------------------- registered buffers ----
 // Every check here uses values identical on every rank (the schedule asked
 // for, the byte count, the channel kind, whether the stream is being
@@ -2283,6 +2315,52 @@ void Communicator::LaunchReduceScatter(const KernelSet& ks, char* buf, const uin
         hip_check(ks.rscatter(a, grid, stream), "launch mesh reduce-scatter");
     }
     trace_ = nullptr;  // reduce-scatter launches are not traced
+}
+
+// The rooted reduce's schedule over the chunk byte ranges of `buf`:
+// PlanReduceToRanges' launches of k_rooted (the mesh's pieces and tiles on
+// every rank; all three roles on the root, scatter and reduce elsewhere),
+// shaped like a mesh allreduce of `total` bytes (RdcCommTune / RDC_NBLOCKS /
+// RDC_TILE_BYTES apply), the grid clamped by k_rooted's own occupancy — the
+// same clamp on every rank, so every rank cuts the same tiles.
+void Communicator::LaunchReduceTo(const KernelSet& ks, char* buf, const uint64_t* off, const uint64_t* len,
+                                  uint64_t total, size_t esz, int root, hipStream_t stream) {
+    const Shape sh = ShapeFor(total, RDC_ALGO_MESH);
+    const int grid_cap =
+        LaunchGrid(sh.max_blocks > 0 ? sh.max_blocks : 2 * cus_min_, ks.occupancy(RDC_KIND_ROOTED, n_));
+    const std::vector<Piece> plan =
+        PlanReduceToRanges(n_, rank_, root, off, len, esz, layout(), sh.tile_bytes, grid_cap, sh.split);
+    for (const Piece& p : plan) {
+        CollArgs a;
+        FillArgsCommon(&a);
+        if (&p == &plan.back()) {
+            a.notify = notify_;
+            a.notify_val = notify_val_;
+            notify_ = nullptr;
+        }
+        a.user = buf;
+        a.root = root;
+        memcpy(a.off, p.off, sizeof(a.off));
+        memcpy(a.len, p.len, sizeof(a.len));
+        memcpy(a.mis, p.mis, sizeof(a.mis));
+        memcpy(a.tiles, p.tiles, sizeof(a.tiles));
+        a.tile_bytes = p.tile_bytes;
+        a.nb_scatter = p.nb_scatter;
+        a.nb_reduce = p.nb_reduce;
+        a.nb_gather = p.nb_gather;
+        a.kind = RDC_KIND_ROOTED;
+        ++seq_;
+        const int grid = p.nb_scatter + p.nb_reduce + p.nb_gather;
+        last_launch_[0] = (uint64_t)grid;
+        last_launch_[1] = (uint64_t)p.nb_scatter;
+        last_launch_[2] = (uint64_t)p.nb_reduce;
+        last_launch_[3] = (uint64_t)p.nb_gather;
+        last_launch_[4] = p.tile_bytes;
+        last_launch_[5] = RDC_ALGO_MESH;
+        log_launch(this, seq_, RDC_ALGO_MESH, total, grid, p.tile_bytes);
+        hip_check(ks.rooted(a, grid, stream), "launch rooted reduce");
+    }
+    trace_ = nullptr;  // rooted reduce launches are not traced
 }
 
 // Staging image of the coalesced path, grown on demand (never shrinks).  The

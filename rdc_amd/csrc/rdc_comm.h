@@ -236,6 +236,13 @@ public:
     // (no tree branch: rdc_reduce_ring_mincount does not apply); every other
     // byte of buf stays as passed.  algo: auto, RDC_ALGO_MESH or RDC_ALGO_DIRECT.
     void ReduceScatter(void* buf, size_t count, int dtype, int op, hipStream_t stream, int algo = RDC_ALGO_AUTO);
+    // In-place device reduction to `root` (MPI_Reduce), stream-ordered: on the
+    // root all count elements receive the bits Allreduce's ring order puts
+    // there, at every size; on every other rank buf is only read.  Refused
+    // before any launch (std::invalid_argument): a root outside [0, n), an
+    // unsupported (dtype, op), a misaligned or null buffer.  root must be the
+    // same on every rank.  n == 1 or count == 0: nothing is launched.
+    void ReduceTo(void* buf, size_t count, int dtype, int op, int root, hipStream_t stream);
     // bucketed allreduce: the result of Allreduce on every buffer in order
     // (bit-identical), moved as fused launches over a chunk-major staging image
     void AllreduceCoalesced(void* const* bufs, const size_t* counts, int nbuf, int dtype, int op,
@@ -446,6 +453,9 @@ private:
     // the scratch schedule of a reduce-scatter (k_rscatter) over chunk byte ranges of buf
     void LaunchReduceScatter(const KernelSet& ks, char* buf, const uint64_t* off, const uint64_t* len, uint64_t total,
                              size_t esz, hipStream_t stream);
+    // the scratch schedule of a rooted reduce (k_rooted) over chunk byte ranges of buf
+    void LaunchReduceTo(const KernelSet& ks, char* buf, const uint64_t* off, const uint64_t* len, uint64_t total,
+                        size_t esz, int root, hipStream_t stream);
     // one all-to-all launch over validated segments; equal_len: the equal split's bytes per peer
     // of this launch (PlanAlltoall's tile rule), 0 for alltoallv
     void LaunchAlltoall(const char* send, const uint64_t* send_off, const uint64_t* send_len, char* recv,

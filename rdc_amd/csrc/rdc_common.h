@@ -43,10 +43,12 @@ enum {
 // launch of kind RDC_KIND_DIRECT.  RDC_KIND_RSCATTER: the mesh reduce-scatter,
 // whose launches end only after every peer's done word arrived.
 // RDC_KIND_ALLTOALL: the personalised exchange (k_alltoall), the allgather's
-// slot protocol with a different segment per destination)
+// slot protocol with a different segment per destination.
+// RDC_KIND_ROOTED: the reduction to one rank (k_rooted), the mesh's slots with
+// results going to the root only; ends like RDC_KIND_RSCATTER)
 enum { RDC_KIND_NONE = 0, RDC_KIND_MESH = 1, RDC_KIND_RING = 2, RDC_KIND_BCAST = 3, RDC_KIND_ALLGATHER = 4,
        RDC_KIND_ONESHOT = 5, RDC_KIND_TREE = 6, RDC_KIND_DIRECT = 7, RDC_KIND_RSCATTER = 8,
-       RDC_KIND_RSCATTER_DIRECT = 9, RDC_KIND_ALLTOALL = 10 };
+       RDC_KIND_RSCATTER_DIRECT = 9, RDC_KIND_ALLTOALL = 10, RDC_KIND_ROOTED = 11 };
 // RdcCommLastLaunch's algo word (and the RDC_LAUNCH_LOG kind) of an all-to-all
 // launch: not an allreduce schedule, so outside RDC_ALGO_* (broadcast logs 100,
 // allgather 101)
@@ -102,7 +104,7 @@ struct CollArgs {
     char* user;                          // local in-place buffer (byte 0 of the whole buffer)
     int n;                               // ranks
     int rank;
-    int root;                            // broadcast root
+    int root;                            // broadcast root; rooted reduce: the rank that receives the result
     uint64_t tile_bytes;                 // multiple of RDC_SLOT_ALIGN
     int tiles[RDC_MAX_RANKS];            // tiles in chunk c for this launch
     uint64_t off[RDC_MAX_RANKS];         // byte offset of chunk c's piece in `user`
@@ -117,7 +119,8 @@ struct CollArgs {
     char* ag[RDC_MAX_RANKS];             // rank p's allgather scratch region
     uint64_t* flags[RDC_MAX_RANKS];      // rank p's flag region: [2n][max_tiles] + done[n] (rdc_device.h seq)
     char* cbuf[RDC_MAX_RANKS];           // allgather: local buffer of rank c's data (off/len index into it)
-    int nb_scatter, nb_reduce, nb_gather;  // mesh block roles (allgather: push / -, gather; reduce-scatter: no gather)
+    int nb_scatter, nb_reduce, nb_gather;  // mesh block roles (allgather: push / -, gather; reduce-scatter: no gather;
+                                           //   rooted reduce: gather on the root only)
     uint32_t* err;                       // local device error word
     uint32_t* err_mirror;                // host-pinned copy of *err, refreshed by every launch's last block
     uint32_t* notify;                    // optional pinned word: the last block stores notify_val there when

@@ -17,9 +17,11 @@ struct KernelSet {
     // in-place reduce-scatter (chunk r of the reduction on rank r, every other byte untouched):
     hipError_t (*rscatter)(const CollArgs& a, int grid, hipStream_t s);         // scratch schedule (k_rscatter)
     hipError_t (*rscatter_direct)(const CollArgs& a, int grid, hipStream_t s);  // registered buffers (k_rscatter_direct)
+    // in-place reduction to rank a.root, every other rank's buffer untouched (k_rooted, scratch schedule)
+    hipError_t (*rooted)(const CollArgs& a, int grid, hipStream_t s);
     hipError_t (*svc)(const SvcArgs& a, hipStream_t s);  // the small-allreduce service (one block)
     // resident blocks per CU of the kernel a launch of `kind` (RDC_KIND_MESH /
-    // RING / ONESHOT / TREE / DIRECT / RSCATTER / RSCATTER_DIRECT) on n ranks uses (hipOccupancyMaxActiveBlocksPerMultiprocessor,
+    // RING / ONESHOT / TREE / DIRECT / RSCATTER / RSCATTER_DIRECT / ROOTED) on n ranks uses (hipOccupancyMaxActiveBlocksPerMultiprocessor,
     // cached); the grid clamp of ResidentGrid (rdc_plan.h)
     int (*occupancy)(int kind, int n);
 };

@@ -178,8 +178,12 @@ __global__ __launch_bounds__(kBlock) void k_reduce_unaligned(char* dst, const ch
 // tile, written to the local user buffer and to every peer's allgather slot.
 // one element at byte offset e of the tile: ring-order fold of the n ranks'
 // values, stored to the local user buffer and every peer's allgather slot
-// (kPush false: the reduce-scatter's fold — the local user buffer only)
-template <int OP, typename T, bool kPush = true>
+// (kOut: where the result goes.  kOutAll, the allreduce's fold: the local user
+// buffer and every peer's allgather slot.  kOutLocal, the reduce-scatter's:
+// the local user buffer only.  kOutPeer, a rooted reduce's non-root owner:
+// rank a.root's allgather slot only — `own` is read and never stored to)
+enum { kOutLocal = 0, kOutAll = 1, kOutPeer = 2 };
+template <int OP, typename T, int kOut = kOutAll>
 __device__ __forceinline__ void mesh_fold_elem(const CollArgs& a, char* own, const char* slot0, uint64_t soff,
                                                uint64_t e) {
     const int n = a.n, r = a.rank, f = a.fold[r];  // the ring order of chunk f
@@ -189,24 +193,27 @@ __device__ __forceinline__ void mesh_fold_elem(const CollArgs& a, char* own, con
     };
     T acc = val((f - 1 + n) % n);
     for (int k = 2; k <= n; ++k) acc = OpF<OP>::apply(val((f - k + n) % n), acc);
-    *reinterpret_cast<T*>(own + e) = acc;
-    if (kPush)
+    if (kOut != kOutPeer) *reinterpret_cast<T*>(own + e) = acc;
+    if (kOut == kOutAll)
         for (int p = 0; p < n; ++p)
             if (p != r) st_elem_wt<T>(a.ag[p] + soff + e, acc);
+    if (kOut == kOutPeer) st_elem_wt<T>(a.ag[a.root] + soff + e, acc);
 }
 
 // Fold `tlen` bytes: own (this rank's values, overwritten with the result),
 // slot0 (rank q's copy at slot0 + q*slot_bytes) in ring order; the result also
-// goes to every peer's allgather region at byte offset soff (kPush; without
-// it — k_rscatter — nothing leaves this rank and soff is unused).
-template <int OP, typename T, int NMAX, bool kPush = true>
+// goes to every peer's allgather region at byte offset soff (kOutAll; with
+// kOutLocal — k_rscatter — nothing leaves this rank and soff is unused; with
+// kOutPeer — k_rooted off the root — the result goes to rank a.root's
+// allgather region at soff only, and `own` keeps the caller's bytes).
+template <int OP, typename T, int NMAX, int kOut = kOutAll>
 __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, const char* slot0, uint64_t soff, uint64_t tlen) {
     const int n = a.n, r = a.rank, f = a.fold[r];
     const unsigned tid = threadIdx.x;
     if ((((uintptr_t)own ^ (uintptr_t)slot0) & 15) != 0) {
         // this rank's buffer is not 16-B aligned: exact, element by element
         for (uint64_t e = (uint64_t)tid * sizeof(T); e < tlen; e += (uint64_t)kBlock * sizeof(T))
-            mesh_fold_elem<OP, T, kPush>(a, own, slot0, soff, e);
+            mesh_fold_elem<OP, T, kOut>(a, own, slot0, soff, e);
         return;
     }
     const uint64_t mis16 = (uint64_t)(uintptr_t)own & 15;
@@ -216,8 +223,8 @@ __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, 
     const uint64_t tail = head + (nvec << 4);
     {   // element-wise head / tail (< 16 bytes each)
         const uint64_t nh = head / sizeof(T), nt = (tlen - tail) / sizeof(T);
-        if (tid < nh) mesh_fold_elem<OP, T, kPush>(a, own, slot0, soff, tid * sizeof(T));
-        else if (tid >= 64 && tid - 64 < nt) mesh_fold_elem<OP, T, kPush>(a, own, slot0, soff, tail + (tid - 64) * sizeof(T));
+        if (tid < nh) mesh_fold_elem<OP, T, kOut>(a, own, slot0, soff, tid * sizeof(T));
+        else if (tid >= 64 && tid - 64 < nt) mesh_fold_elem<OP, T, kOut>(a, own, slot0, soff, tail + (tid - 64) * sizeof(T));
     }
     // All n contributions of U positions are loaded before folding (NMAX x U
     // 16-B loads in flight per lane); folding one rank at a time inside a
@@ -229,11 +236,12 @@ __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, 
     __amdgpu_buffer_rsrc_t ag_rs[NMAX];
     for (uint64_t ib = 0; ib < nvec; ib += U * stride) {
         const uint64_t i = ib + tid;
-        if (kPush) {
+        if (kOut == kOutAll) {
 #pragma unroll
             for (int p = 0; p < NMAX; ++p)
                 if (p < n && p != r) ag_rs[p] = wt_rsrc(a.ag[p] + soff + head + ib * 16);
         }
+        if (kOut == kOutPeer) ag_rs[0] = wt_rsrc(a.ag[a.root] + soff + head + ib * 16);
         v4u v[U][NMAX];
         bool live[U];
 #pragma unroll
@@ -262,12 +270,13 @@ __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, 
             for (int k = 2; k <= NMAX; ++k)
                 if (k <= n) acc = reduce16<OP, T>(v[u][k - 1], acc);
             const uint64_t b = head + (i + u * stride) * 16;
-            st16(own + b, acc);
-            if (kPush) {
+            if (kOut != kOutPeer) st16(own + b, acc);
+            if (kOut == kOutAll) {
 #pragma unroll
                 for (int p = 0; p < NMAX; ++p)
                     if (p < n && p != r) st16_wt(ag_rs[p], (uint32_t)((tid + u * stride) * 16), acc);
             }
+            if (kOut == kOutPeer) st16_wt(ag_rs[0], (uint32_t)((tid + u * stride) * 16), acc);
         }
     }
 }
@@ -484,11 +493,110 @@ __device__ __forceinline__ void rscatter_body(const CollArgs& a, uint64_t seq) {
         const uint64_t toff = (uint64_t)t * a.tile_bytes;
         uint64_t tlen = a.len[r] - toff;
         if (tlen > a.tile_bytes) tlen = a.tile_bytes;
-        mesh_reduce_range<OP, T, NMAX, false>(a, a.user + a.off[r] + toff, a.rs[r] + a.mis[r] + toff, 0, tlen);
+        mesh_reduce_range<OP, T, NMAX, kOutLocal>(a, a.user + a.off[r] + toff, a.rs[r] + a.mis[r] + toff, 0, tlen);
         if (a.poison) {  // every peer's copy of this tile was read
             __syncthreads();
             for (int k = 1; k < n; ++k)
                 block_poison(a.rs[r] + (uint64_t)((r + k) % n) * a.slot_bytes + a.mis[r] + toff, tlen);
+        }
+    }
+}
+
+// ====================================================== rooted reduce ===
+// The reduction to one rank (MPI_Reduce): at a.root the whole buffer receives
+// the allreduce's ring-order bits, every other rank's buffer is only read.
+// The mesh with its second half narrowed to one destination:
+//   scatter (every rank): rscatter_body's, tile for tile;
+//   reduce  (every rank, chunk r): the root folds into its own buffer
+//           (kOutLocal); a non-root owner folds into the root's AG slot r
+//           only (kOutPeer) and publishes the root's flag (row n + r, tile t);
+//   gather  (root only): AG slot c of every other owner c -> the user buffer.
+// Slot reuse: the RS slots are the mesh's, so the scatter
+// keeps the mesh's gate.  An owner writes the root's AG slot only after it
+// folded the root's contribution to that tile, which the root sent in this
+// launch — after its previous launch, the slots' last reader, ended.  Nothing
+// returns to the non-root ranks, so like k_rscatter the launch ends only after
+// every peer's done word for it (launch_done<true>): all RS slots have then
+// been folded and all AG slots gathered, and no successor needs a gate.
+template <int OP, typename T, int NMAX>
+__device__ __forceinline__ void rooted_body(const CollArgs& a, uint64_t seq) {
+    const int n = a.n, r = a.rank, root = a.root;
+    Abort ab{a.err, wall_clock64() + a.timeout_ticks, a.poll_rmw};
+    int b = blockIdx.x;
+    int tmax = 0;
+    for (int c = 0; c < n; ++c) tmax = a.tiles[c] > tmax ? a.tiles[c] : tmax;
+    __shared__ uint64_t* s_flags[RDC_MAX_RANKS];
+
+    if (b < a.nb_scatter) {
+        // ---- scatter: my copy of chunk c's tile t -> owner c's rs slot r
+        const int items = (n - 1) * tmax;
+        // the same slots as the mesh's scatter, so the same gate: after a
+        // one-shot launch the owners may still be reading their RS slots
+        if (b < items && prev_kind(a) == RDC_KIND_ONESHOT &&
+            !gate_on_peers(a, seq, r + 1, n - 1, ab, RDC_KERR_TIMEOUT_RS))
+            return;
+        for (int it = b; it < items; it += a.nb_scatter) {
+            const int t = it / (n - 1);
+            const int c = (r + 1 + it % (n - 1)) % n;
+            if (t >= a.tiles[c]) continue;
+            const uint64_t toff = (uint64_t)t * a.tile_bytes;
+            uint64_t tlen = a.len[c] - toff;
+            if (tlen > a.tile_bytes) tlen = a.tile_bytes;
+            char* dst = a.rs[c] + (uint64_t)r * a.slot_bytes + a.mis[c];
+            block_copy<kDstPeer>(dst + toff, a.user + a.off[c] + toff, tlen);
+            block_publish1(flag_word(a, c, (uint64_t)r * a.max_tiles + t), seq, a.uc);
+        }
+        return;
+    }
+    b -= a.nb_scatter;
+    if (b < a.nb_reduce) {
+        // ---- reduce: chunk r, tile t, once all n-1 contributions landed
+        for (int t = b; t < a.tiles[r]; t += a.nb_reduce) {
+            if (threadIdx.x < (unsigned)(n - 1)) {
+                const int p = (r + 1 + threadIdx.x) % n;
+                s_flags[threadIdx.x] = flag_word(a, r, (uint64_t)p * a.max_tiles + t);
+            }
+            __syncthreads();
+            if (!block_wait(s_flags, n - 1, seq, ab, RDC_KERR_TIMEOUT_RS, a.uc)) return;
+            const uint64_t toff = (uint64_t)t * a.tile_bytes;
+            uint64_t tlen = a.len[r] - toff;
+            if (tlen > a.tile_bytes) tlen = a.tile_bytes;
+            char* own = a.user + a.off[r] + toff;
+            const char* slot0 = a.rs[r] + a.mis[r] + toff;
+            if (r == root)
+                mesh_reduce_range<OP, T, NMAX, kOutLocal>(a, own, slot0, 0, tlen);
+            else  // the user buffer is read only: the result leaves for the root's AG slot r
+                mesh_reduce_range<OP, T, NMAX, kOutPeer>(a, own, slot0, (uint64_t)r * a.slot_bytes + a.mis[r] + toff,
+                                                         tlen);
+            if (a.poison) {  // every peer's copy of this tile was read: before the result's publish
+                __syncthreads();
+                for (int k = 1; k < n; ++k)
+                    block_poison(a.rs[r] + (uint64_t)((r + k) % n) * a.slot_bytes + a.mis[r] + toff, tlen);
+            }
+            if (r != root) block_publish1(flag_word(a, root, (uint64_t)(n + r) * a.max_tiles + t), seq, a.uc);
+        }
+        return;
+    }
+    b -= a.nb_reduce;
+    // ---- gather (nb_gather > 0 on the root only): owner c's result tile t -> my user buffer
+    const int items = (n - 1) * tmax;
+    for (int it = b; it < items; it += a.nb_gather) {
+        const int t = it / (n - 1);
+        const int c = (r + 1 + it % (n - 1)) % n;
+        if (t >= a.tiles[c]) continue;
+        if (threadIdx.x == 0) s_flags[0] = flag_word(a, r, (uint64_t)(n + c) * a.max_tiles + t);
+        __syncthreads();
+        if (!block_wait(s_flags, 1, seq, ab, RDC_KERR_TIMEOUT_AG, a.uc)) return;
+        const uint64_t toff = (uint64_t)t * a.tile_bytes;
+        uint64_t tlen = a.len[c] - toff;
+        if (tlen > a.tile_bytes) tlen = a.tile_bytes;
+        char* src = a.ag[r] + (uint64_t)c * a.slot_bytes + a.mis[c];
+        block_copy_pull(a.user + a.off[c] + toff, src + toff, tlen);
+        // owner c rewrites this slot only in a later launch, which starts
+        // after this one's end (launch_done<true>)
+        if (a.poison) {
+            __syncthreads();
+            block_poison(src + toff, tlen);
         }
     }
 }
@@ -1413,6 +1521,14 @@ __global__ __launch_bounds__(kBlock) void k_rscatter(CollArgs a) {
     launch_done<true>(a, seq);
 }
 
+// rooted reduce, scratch schedule (RDC_KIND_ROOTED)
+template <int OP, typename T, int NMAX>
+__global__ __launch_bounds__(kBlock) void k_rooted(CollArgs a) {
+    uint64_t seq;
+    if (!launch_begin(a, &seq)) rooted_body<OP, T, NMAX>(a, seq);
+    launch_done<true>(a, seq);
+}
+
 // reduce-scatter between registered buffers (a launch of kind RDC_KIND_DIRECT:
 // peers read this rank's buffer, so launch_done waits for them as for k_direct)
 template <int OP, typename T, int NMAX>
@@ -1864,6 +1980,13 @@ struct Kernels {
             hipLaunchKernelGGL((k_rscatter_direct<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
         return hipGetLastError();
     }
+    static hipError_t rooted(const CollArgs& a, int grid, hipStream_t s) {
+        if (a.n <= 8)
+            hipLaunchKernelGGL((k_rooted<OP, T, 8>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
+        else
+            hipLaunchKernelGGL((k_rooted<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
+        return hipGetLastError();
+    }
     static hipError_t ring(const CollArgs& a, int grid, hipStream_t s) {
         hipLaunchKernelGGL((k_ring<OP, T>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
         return hipGetLastError();
@@ -1889,8 +2012,9 @@ struct Kernels {
     }
     static int occupancy(int kind, int n) {
         // [mesh 8, mesh 16, oneshot 8, oneshot 16, ring, tree 8, tree 16, direct 8, direct 16,
-        //  rscatter 8, rscatter 16, rscatter direct 8, rscatter direct 16]; 0 = not queried yet
-        static int cache[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        //  rscatter 8, rscatter 16, rscatter direct 8, rscatter direct 16, rooted 8, rooted 16];
+        // 0 = not queried yet
+        static int cache[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         const int wide = n > 8 ? 1 : 0;
         const int slot = kind == RDC_KIND_RING      ? 4
                          : kind == RDC_KIND_TREE    ? 5 + wide
@@ -1898,6 +2022,7 @@ struct Kernels {
                          : kind == RDC_KIND_DIRECT  ? 7 + wide
                          : kind == RDC_KIND_RSCATTER ? 9 + wide
                          : kind == RDC_KIND_RSCATTER_DIRECT ? 11 + wide
+                         : kind == RDC_KIND_ROOTED  ? 13 + wide
                                                     : wide;
         if (cache[slot] > 0) return cache[slot];
         int b = 0;
@@ -1915,6 +2040,8 @@ struct Kernels {
             case 10: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter<OP, T, 16>, kBlock, debug_lds_pad()); break;
             case 11: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter_direct<OP, T, 8>, kBlock, debug_lds_pad()); break;
             case 12: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter_direct<OP, T, 16>, kBlock, debug_lds_pad()); break;
+            case 13: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rooted<OP, T, 8>, kBlock, debug_lds_pad()); break;
+            case 14: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rooted<OP, T, 16>, kBlock, debug_lds_pad()); break;
             default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_ring<OP, T>, kBlock, debug_lds_pad()); break;
         }
         if (e != hipSuccess || b <= 0) {
@@ -1934,6 +2061,7 @@ struct Kernels {
     ks->direct = &Kernels<OP, T>::direct; \
     ks->rscatter = &Kernels<OP, T>::rscatter; \
     ks->rscatter_direct = &Kernels<OP, T>::rscatter_direct; \
+    ks->rooted = &Kernels<OP, T>::rooted; \
     ks->oneshot = &Kernels<OP, T>::oneshot; \
     ks->tree = &Kernels<OP, T>::tree;       \
     ks->svc = &Kernels<OP, T>::svc;         \

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <functional>
 #include <queue>
+#include <stdexcept>
 #include <unordered_map>
 #include <unordered_set>
 
@@ -169,6 +170,32 @@ std::vector<Piece> PlanReduceScatter(int n, uint64_t count, size_t esz, const La
         len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
     }
     return PlanReduceScatterRanges(n, off, len, esz, L, cfg_tile, max_blocks, split);
+}
+
+std::vector<Piece> PlanReduceToRanges(int n, int rank, int root, const uint64_t* off, const uint64_t* len, size_t esz,
+                                      const Layout& L, size_t cfg_tile, int max_blocks, MeshSplit split) {
+    if (n > 1 && (rank < 0 || rank >= n || root < 0 || root >= n))
+        throw std::invalid_argument("rdc: rooted reduce: rank or root outside [0, n)");
+    // The pieces, tiles and slots never depend on rank or root (both ends of
+    // every hand-off cut alike); only the roles do: the root runs all three of
+    // the mesh, every other rank the reduce-scatter's two
+    if (rank == root) return PlanAllreduceRanges(n, off, len, esz, L, RDC_ALGO_MESH, cfg_tile, max_blocks, split);
+    return PlanReduceScatterRanges(n, off, len, esz, L, cfg_tile, max_blocks, split);
+}
+
+std::vector<Piece> PlanReduceTo(int n, int rank, int root, uint64_t count, size_t esz, const Layout& L,
+                                size_t cfg_tile, int max_blocks, MeshSplit split) {
+    if (n > 1 && (rank < 0 || rank >= n || root < 0 || root >= n))
+        throw std::invalid_argument("rdc: rooted reduce: rank or root outside [0, n)");
+    if (n <= 1 || count == 0 || esz == 0) return std::vector<Piece>();
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, n, cb, ce);
+    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
+    for (int c = 0; c < n; ++c) {
+        off[c] = (uint64_t)cb[c] * esz;
+        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
+    }
+    return PlanReduceToRanges(n, rank, root, off, len, esz, L, cfg_tile, max_blocks, split);
 }
 
 uint64_t OneshotHalfBytes(const Layout& L) { return round_down(L.slot_bytes / 2, RDC_SLOT_ALIGN); }
@@ -620,6 +647,40 @@ HbmBytes ModelAlltoallBytes(int n, int rank, const uint64_t* send_len, const uin
     h.read_max = h.read_sum = send_all + recv_peers;
     h.write_max = h.write_sum = send_peers + recv_all;
     h.egress_max = send_peers;
+    return h;
+}
+
+// One rooted reduce on rank `rank`, in the same conventions, per the loops of
+// k_rooted:
+//   every rank: scatter every other chunk to its owner (load user, store
+//               remote: egress); fold own chunk (load n-1 slots + user)
+//   non-root:   the folded chunk goes to the root's AG slot (store remote:
+//               egress); nothing is stored locally
+//   root:       the folded chunk goes to its own buffer; gather every other
+//               chunk (load own AG slot, store user)
+// rank < 0: the maxima and sums over all ranks.
+HbmBytes ModelReduceToBytes(int n, int rank, int root, uint64_t count, size_t esz) {
+    HbmBytes h;
+    if (n < 2 || count == 0) return h;
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, n, cb, ce);
+    const uint64_t S = count * esz;
+    for (int r = 0; r < n; ++r) {
+        if (rank >= 0 && r != rank) continue;
+        const uint64_t own = (uint64_t)(ce[r] - cb[r]) * esz, others = S - own;
+        uint64_t rd = others + (uint64_t)n * own, wr = others + own, eg = others;
+        if (r == root) {
+            rd += others;
+            wr += others;
+        } else {
+            eg += own;
+        }
+        h.read_max = std::max(h.read_max, rd);
+        h.write_max = std::max(h.write_max, wr);
+        h.read_sum += rd;
+        h.write_sum += wr;
+        h.egress_max = std::max(h.egress_max, eg);
+    }
     return h;
 }
 

@@ -184,6 +184,20 @@ std::vector<Piece> PlanReduceScatterRanges(int n, const uint64_t* off, const uin
 std::vector<Piece> PlanReduceScatter(int n, uint64_t count, size_t esz, const Layout& L, size_t cfg_tile,
                                      int max_blocks, MeshSplit split = MeshSplit());
 
+// ------------------------------------------------------- rooted reduce ---
+// The reduction to one rank (MPI_Reduce; Communicator::ReduceTo): the launches
+// of k_rooted on rank `rank`.  off / len / mis / tiles / tile_bytes and the
+// cutting of chunks beyond one slot are PlanAllreduceRanges' for the mesh and
+// depend on neither rank nor root: both ends of every hand-off cut alike.
+// Only the roles differ: the root gets the mesh's scatter / reduce / gather
+// split, every other rank PlanReduceScatterRanges' (nb_gather = 0).  Throws
+// std::invalid_argument for a rank or root outside [0, n).
+std::vector<Piece> PlanReduceToRanges(int n, int rank, int root, const uint64_t* off, const uint64_t* len, size_t esz,
+                                      const Layout& L, size_t cfg_tile, int max_blocks,
+                                      MeshSplit split = MeshSplit());
+std::vector<Piece> PlanReduceTo(int n, int rank, int root, uint64_t count, size_t esz, const Layout& L,
+                                size_t cfg_tile, int max_blocks, MeshSplit split = MeshSplit());
+
 // ------------------------------------------------------ tree allreduce ---
 // rdc_reduce_ring_mincount (communicator_manager.cc:46): TryAllreduce takes
 // TryAllreduceTree for buffers of at most that many bytes
@@ -249,6 +263,10 @@ struct HbmBytes {
 HbmBytes ModelHbmBytes(int n, uint64_t count, size_t esz, int algo);
 // The same model of one reduce-scatter (algo RDC_ALGO_MESH or RDC_ALGO_DIRECT)
 HbmBytes ModelReduceScatterBytes(int n, uint64_t count, size_t esz, int algo);
+// The same model of one rooted reduce on rank `rank` (the root also reads its
+// AG slots and stores the gathered chunks; a non-root rank's result store is
+// remote: egress).  rank < 0: the maxima and sums over all n ranks
+HbmBytes ModelReduceToBytes(int n, int rank, int root, uint64_t count, size_t esz);
 // The same model of one all-to-all on rank `rank` (one rank's row send_len and
 // column recv_len of the size matrix, so max = sum = this rank's bytes):
 // reads = the send buffer + this rank's own slots, writes = the peers' slots

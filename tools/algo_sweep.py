@@ -24,6 +24,16 @@ synchronise after every call, which is what the point-to-point form does (its
 waits complete every call); "speedup" compares the two synchronised forms.  Next to
 them the all-to-all's share of the HBM peak by RdcPlanAlltoallBytes (every
 rank's bytes: the ranks share one GPU).
+SWEEP_COLLECTIVE=reduce_to times RdcCommReduceTo (root 0) and, on the same
+communicator and buffer, the mesh allreduce (algo 2) and the automatic
+allreduce (algo 0: what a caller who needs the sum on one rank uses today), in
+alternating rounds (SWEEP_ROUNDS, default 5), each form pipelined (<name>) and
+synchronised per call (<name>_sync): the median over rounds of the slowest
+rank's time per call and the spread.  Next to them reduce_to_bytes_ratio = the
+rooted reduce's modelled HBM bytes (read + write, summed over the ranks) over
+the mesh allreduce's (RdcPlanReduceToBytes / RdcPlanHbmBytes), and
+reduce_to_hbm_fraction = those bytes per pipelined call over the HBM peak (the
+ranks share one GPU).
 
     python -m torch.distributed.run --nproc-per-node N tools/algo_sweep.py [sizes_MiB] [steps]
 """
@@ -120,6 +130,86 @@ def alltoall_sweep(sizes, steps, rank, world, comm, sp):
                           "hbm_peak_bytes_per_s": HBM_PEAK}), flush=True)
 
 
+def reduce_to_sweep(sizes, steps, rank, world, comm, sp):
+    """Per size, `rounds` rounds alternating the three forms on one buffer; a
+    round's time is the slowest rank's, the figure the median over rounds."""
+    import torch
+    import torch.distributed as dist
+    import rdc_amd
+    from rdc_amd._lib import _LIB, check_call
+    rounds = int(os.environ.get("SWEEP_ROUNDS", "5"))
+    big = int(max(sizes) * (1 << 20))
+    buf = torch.empty(big // 4, dtype=torch.float32, device="cuda")
+    rdc_amd.fill_(buf, 0x5EED0000, rank)
+    p = ctypes.c_void_p(buf.data_ptr())
+    out = {}
+    for mib in sizes:
+        nb = int(mib * (1 << 20))
+
+        def rooted():
+            check_call(_LIB.RdcCommReduceTo(comm.handle, p, nb // 4, 6, 2, 0, sp))
+
+        def mesh():
+            check_call(_LIB.RdcCommAllreduceEx(comm.handle, p, nb // 4, 6, 2, 2, sp))
+
+        def auto():
+            check_call(_LIB.RdcCommAllreduceEx(comm.handle, p, nb // 4, 6, 2, 0, sp))
+
+        def timed(fn, n_steps, sync):
+            torch.cuda.synchronize()
+            dist.barrier()
+            t0 = time.perf_counter()
+            for _ in range(n_steps):
+                fn()
+                if sync:
+                    torch.cuda.synchronize()
+            torch.cuda.synchronize()
+            t = torch.tensor([(time.perf_counter() - t0) / n_steps], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            return float(t[0])
+
+        forms = (("reduce_to", rooted), ("allreduce_mesh", mesh), ("allreduce_auto", auto))
+        n_steps = max(steps, min(500, int(2e8 // max(nb, 1))))
+        for _, fn in forms:
+            for _ in range(3):
+                fn()
+        comm.check(sp)
+        ts = {}
+        ll = (ctypes.c_uint64 * 6)()
+        for _ in range(rounds):
+            for name, fn in forms:
+                ts.setdefault(name, []).append(timed(fn, n_steps, False))
+                ts.setdefault(name + "_sync", []).append(timed(fn, min(n_steps, 100), True))
+        comm.check(sp)
+        row = {}
+        for name, v in ts.items():
+            v.sort()
+            med = v[len(v) // 2]
+            row[name] = round(med * 1e3, 4)
+            row[name + "_spread"] = round((v[-1] - v[0]) / med, 3)
+        auto()
+        check_call(_LIB.RdcCommLastLaunch(comm.handle, ll))
+        row["auto_schedule"] = {1: "ring", 2: "mesh", 3: "oneshot", 4: "tree", 5: "mesh_pull",
+                                6: "direct"}.get(int(ll[5]), int(ll[5]))
+        rooted()
+        check_call(_LIB.RdcCommLastLaunch(comm.handle, ll))
+        comm.check(sp)
+        row["root_grid_scatter_reduce_gather_tile"] = [int(x) for x in ll[:5]]
+        m, full = (ctypes.c_uint64 * 5)(), (ctypes.c_uint64 * 5)()
+        check_call(_LIB.RdcPlanReduceToBytes(world, -1, 0, nb // 4, 6, m))
+        check_call(_LIB.RdcPlanHbmBytes(world, nb // 4, 6, 2, full))
+        row["reduce_to_bytes_ratio"] = round((m[2] + m[3]) / float(full[2] + full[3]), 4)
+        row["reduce_to_hbm_fraction"] = round((m[2] + m[3]) / (row["reduce_to"] * 1e-3) / HBM_PEAK, 4)
+        row["speedup_vs_mesh"] = round(row["allreduce_mesh"] / row["reduce_to"], 3)
+        row["speedup_vs_auto"] = round(row["allreduce_auto"] / row["reduce_to"], 3)
+        row["speedup_vs_mesh_sync"] = round(row["allreduce_mesh_sync"] / row["reduce_to_sync"], 3)
+        row["speedup_vs_auto_sync"] = round(row["allreduce_auto_sync"] / row["reduce_to_sync"], 3)
+        out["%g MiB" % mib] = row
+    if rank == 0:
+        print(json.dumps({"algo_sweep_ms_per_call": out, "world": world, "collective": "reduce_to", "root": 0,
+                          "rounds": rounds, "ranks_share_gpu": True, "hbm_peak_bytes_per_s": HBM_PEAK}), flush=True)
+
+
 def main():
     sizes = [float(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "1,4,16,64,256").replace("/", ",").split(",")]
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -135,6 +225,11 @@ def main():
     sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     if os.environ.get("SWEEP_COLLECTIVE", "allreduce") == "alltoall":
         alltoall_sweep(sizes, steps, rank, world, comm, sp)
+        dist.barrier()
+        rdc_amd.finalize()
+        return
+    if os.environ.get("SWEEP_COLLECTIVE", "allreduce") == "reduce_to":
+        reduce_to_sweep(sizes, steps, rank, world, comm, sp)
         dist.barrier()
         rdc_amd.finalize()
         return
