@@ -340,6 +340,14 @@ public:
     virtual void ReduceTo(void* sendrecvbuf, uint64_t count, mpi::DataType dtype, mpi::OpType op, int root) {
         detail::Check(RdcReduceToOn(handle_, sendrecvbuf, count, (int)dtype, (int)op, root), "ReduceTo");
     }
+    /*! \brief in-place prefix reduction across ranks (host or device memory;
+     *  MPI_Scan, exclusive: MPI_Exscan): rank r ends with the left fold of
+     *  ranks 0..r (exclusive: 0..r-1, r > 0) in rank order; rank 0's buffer is
+     *  only read */
+    virtual void Scan(void* sendrecvbuf, uint64_t count, mpi::DataType dtype, mpi::OpType op, bool exclusive) {
+        detail::Check(RdcScanOn(handle_, sendrecvbuf, count, (int)dtype, (int)op, exclusive ? 1 : 0),
+                      exclusive ? "Exscan" : "Scan");
+    }
     /*! \brief allreduce with a custom HOST reducer (communicator.h:92-93, virtual
      *  here).  sendrecvbuf needs an item size (Count()).  Ring order per Split
      *  chunk above rdc_reduce_ring_mincount bytes, the tree's order at or below
@@ -671,6 +679,24 @@ inline std::pair<uint64_t, uint64_t> ReduceScatter(DType* sendrecvbuf, uint64_t 
 template <typename OP, typename DType>
 inline void ReduceTo(DType* sendrecvbuf, uint64_t count, int root, const std::string& comm_name = kMainCommName) {
     GetCommunicator(comm_name)->ReduceTo(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType, root);
+}
+
+/*! \brief in-place inclusive prefix reduction across ranks (MI355X addition to
+ *  the public surface; MPI_Scan).  Rank r ends with y[r], where y[0] = x[0] and
+ *  y[q] = OP::Reduce(dst = y[q-1], src = x[q]), element by element; rank 0's
+ *  buffer stays exactly as passed.  For a floating-point Sum the last rank's
+ *  result does not have Allreduce's ring-order bits */
+template <typename OP, typename DType>
+inline void Scan(DType* sendrecvbuf, uint64_t count, const std::string& comm_name = kMainCommName) {
+    GetCommunicator(comm_name)->Scan(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType, false);
+}
+
+/*! \brief in-place exclusive prefix reduction across ranks (MPI_Exscan): rank
+ *  r > 0 ends with Scan's result of rank r-1; rank 0's buffer stays exactly as
+ *  passed (MPI leaves it undefined) */
+template <typename OP, typename DType>
+inline void Exscan(DType* sendrecvbuf, uint64_t count, const std::string& comm_name = kMainCommName) {
+    GetCommunicator(comm_name)->Scan(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType, true);
 }
 
 /*! \brief out-of-place all-to-all, equal split (MI355X addition to the public

@@ -123,6 +123,30 @@ int RdcReduceScatterOn(void* comm, void* sendrecv, size_t count, int dtype, int 
 int RdcReduceTo(void* sendrecv, size_t count, int dtype, int op, int root);
 int RdcReduceToOn(void* comm, void* sendrecv, size_t count, int dtype, int op, int root);
 
+/* Prefix reduction across ranks, in place (MPI_Scan; exclusive = 1: MPI_Exscan;
+ * MI355X addition: the reference has no scan).  With x[q] rank q's input, y[0]
+ * = x[0] and y[q] = OP::Reduce(dst = y[q-1], src = x[q]): a left fold in rank
+ * order, element by element, so tiling and piece cuts cannot change a bit.
+ * Inclusive (exclusive = 0): rank r ends with y[r].  Exclusive (exclusive = 1):
+ * rank r > 0 ends with y[r-1].  On rank 0 sendrecv is only read in both modes:
+ * every byte stays exactly as passed (MPI leaves rank 0's exscan result
+ * undefined; here it is defined).  The running prefix is always the dst
+ * operand of op::Reducer: for Max / Min a NaN in the prefix sticks and a NaN in
+ * x[q] is ignored; signed sums wrap; fp16 / bf16 round per hop.  For a
+ * floating-point Sum y[n-1] does NOT have the bits RdcAllreduce leaves (its
+ * ring order starts each chunk at another rank; this fold always starts at
+ * rank 0).  rdc_reduce_ring_mincount is not consulted: the reference has no
+ * scan and no tree branch applies.  The (dtype, op) pairs are the allreduce's.
+ * Refused with a message in RdcGetLastError before anything is launched: an
+ * unsupported (dtype, op), a buffer not aligned to its element size, a null
+ * buffer with count > 0, `exclusive` outside {0, 1}.  count = 0 or world size 1
+ * succeed without touching the GPU and consume no launch number.  Host or
+ * device memory (detected); synchronous.  A host buffer goes up whole on every
+ * rank and the whole result is copied back on every rank but 0: rank 0's host
+ * buffer is never written.  RdcScan uses the "main" communicator. */
+int RdcScan(void* sendrecv, size_t count, int dtype, int op, int exclusive);
+int RdcScanOn(void* comm, void* sendrecv, size_t count, int dtype, int op, int exclusive);
+
 /* All-to-all, out of place (MI355X addition: the reference has no personalised
  * exchange; its custom-reducer allreduce builds one out of ISend / IRecv).
  * On rank r, bytes [send_off[p], send_off[p] + send_len[p]) of `send` land at
@@ -303,6 +327,20 @@ int RdcCommAllgather(void* comm, void** dev_bufs, const size_t* sizes, void* str
  * the same bytes.  RdcCommLastLaunch reports algo 2, and gather blocks on the
  * root only. */
 int RdcCommReduceTo(void* comm, void* dev_buf, size_t count, int dtype, int op, int root, void* stream);
+/* Device-resident in-place scan / exscan (see RdcScan for the result and the
+ * refusals), stream-ordered; errors raised inside the kernel surface at
+ * RdcCommCheck.  One schedule, on the scratch path (k_scan): the ring's reduce
+ * step without the wrap-around, pipelined tile by tile down the rank order —
+ * rank 0 copies a tile into rank 1's scratch, rank r folds what it received
+ * with its own tile, stores its result and, in the same pass, the prefix into
+ * rank r+1's scratch.  Buffers beyond one scratch slot run as several launches.
+ * Works in single-process groups and can be captured in a hipGraph.  A launch
+ * ends only after every peer's launch ended, so the scratch slots need no gate
+ * in whatever launch follows.  RdcCommTune / RDC_NBLOCKS / RDC_TILE_BYTES apply
+ * as for a ring allreduce of the same bytes, except that a configured tile has
+ * no 16 KiB floor.  RdcCommLastLaunch reports {grid, grid, 0, 0, tile bytes,
+ * 103}. */
+int RdcCommScan(void* comm, void* dev_buf, size_t count, int dtype, int op, int exclusive, void* stream);
 /* Device-resident all-to-all (see RdcAlltoall / RdcAlltoallv for the result,
  * the contract and the refusals), stream-ordered; the scratch path (k_alltoall:
  * every rank pushes segment p into peer p's allgather slot `rank` and lands its
@@ -560,6 +598,24 @@ int RdcPlanReduceTo(int n, int rank, int root, size_t count, int dtype, int op, 
  * out5 as RdcPlanHbmBytes (for one rank max = sum); rank < 0: the maxima and
  * sums over all n ranks. */
 int RdcPlanReduceToBytes(int n, int rank, int root, size_t count, int dtype, uint64_t* out5);
+
+/* The launches of a scan / exscan (RdcCommScan) in RdcPlanAllreduce's records:
+ * every piece uses off[0] / len[0] / tiles[0] (mis 0: its image starts at the
+ * slot's base) and word 1 is its grid, min(tiles, max_blocks).  The pieces tile
+ * the buffer in order; a piece has at most min(RdcPlanAlltoallCap, flag-row
+ * length x tile) bytes.  Tile bytes: tile_bytes if not 0 (a multiple of 256),
+ * else the piece's bytes / max_blocks rounded up to 256, within [64 KiB,
+ * 1 MiB].  Nothing depends on `rank` (both ends of every hand-off cut alike);
+ * it is only checked.  Refused: a rank outside [0, n), an unsupported (dtype,
+ * op), tile_bytes not a multiple of 256. */
+int RdcPlanScan(int n, int rank, size_t count, int dtype, int op, size_t scratch_bytes, size_t tile_bytes,
+                int max_blocks, uint64_t* out, int max_pieces, int* out_pieces);
+/* RdcPlanHbmBytes' model of one scan / exscan of S = count elements on rank
+ * `rank`: rank 0 loads S and stores S remotely (egress); 0 < r < n-1 loads 2 S
+ * and stores 2 S, one of them remotely; rank n-1 loads 2 S and stores S.  out5
+ * as RdcPlanHbmBytes (for one rank max = sum); rank < 0: the maxima and sums
+ * over all n ranks. */
+int RdcPlanScanBytes(int n, int rank, size_t count, int dtype, uint64_t* out5);
 
 /* The one launch of an all-to-all as rank `rank` plans it from its row
  * (send_len[n]) and column (recv_len[n]) of the size matrix.  out (36 words):

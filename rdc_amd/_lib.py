@@ -56,6 +56,11 @@ def _load():
         "RdcCommReduceTo": (i, [vp, vp, sz, i, i, i, vp]),
         "RdcPlanReduceTo": (i, [i, i, i, sz, i, i, sz, sz, i, ctypes.POINTER(u64), i, ctypes.POINTER(ctypes.c_int)]),
         "RdcPlanReduceToBytes": (i, [i, i, i, sz, i, ctypes.POINTER(u64)]),
+        "RdcScan": (i, [vp, sz, i, i, i]),
+        "RdcScanOn": (i, [vp, vp, sz, i, i, i]),
+        "RdcCommScan": (i, [vp, vp, sz, i, i, i, vp]),
+        "RdcPlanScan": (i, [i, i, sz, i, i, sz, sz, i, ctypes.POINTER(u64), i, ctypes.POINTER(ctypes.c_int)]),
+        "RdcPlanScanBytes": (i, [i, i, sz, i, ctypes.POINTER(u64)]),
         "RdcAlltoall": (i, [vp, vp, sz]),
         "RdcAlltoallOn": (i, [vp, vp, vp, sz]),
         "RdcAlltoallv": (i, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp, ctypes.POINTER(sz), ctypes.POINTER(sz)]),

@@ -159,6 +159,23 @@ class Comm(object):
                                         _dev.dtype_enum(tensor.dtype), int(op), int(root), s))
         return tensor
 
+    def scan(self, tensor, op, exclusive=False, stream=None):
+        """In-place prefix reduction of a contiguous ROCm tensor across ranks
+        (RdcCommScan; MPI_Scan, ``exclusive=True``: MPI_Exscan): rank r ends
+        with the left fold of ranks 0..r (exclusive: 0..r-1, r > 0) in rank
+        order, element by element; on rank 0 the tensor stays exactly as
+        passed.  Returns the tensor.  A contiguous numpy array is scanned
+        synchronously (RdcScanOn), in place likewise; rank 0's array is never
+        written."""
+        from .core import host_scan
+        if not _is_tensor(tensor):
+            return host_scan(tensor, op, exclusive, comm=self)
+        _dev._check_tensor(tensor)
+        s = stream if stream is not None else _dev.current_stream_ptr(tensor.device)
+        check_call(_LIB.RdcCommScan(self.handle, ctypes.c_void_p(tensor.data_ptr()), tensor.numel(),
+                                    _dev.dtype_enum(tensor.dtype), int(op), 1 if exclusive else 0, s))
+        return tensor
+
     def allreduce_coalesced(self, tensors, op, algo="auto", stream=None):
         """Bucketed allreduce of a list of contiguous ROCm tensors of one dtype,
         in place: the result of ``allreduce`` on each tensor in order

@@ -301,6 +301,37 @@ def host_reduce(data, op, root, comm=None):
     return data
 
 
+def scan(data, op, exclusive=False):
+    """In-place prefix reduction across ranks on the "main" communicator
+    (RdcScan; MPI_Scan, ``exclusive=True``: MPI_Exscan): rank r ends with the
+    left fold of ranks 0..r (exclusive: 0..r-1, r > 0) in rank order, element
+    by element; on rank 0 ``data`` stays exactly as passed.  A contiguous
+    numpy.ndarray (synchronous) or a ROCm torch.Tensor (stream-ordered on
+    torch's current stream); returns ``data``."""
+    op = int(Op(op) if not isinstance(op, Op) else op)
+    if type(data).__module__.startswith("torch"):
+        from . import comm as _comm
+        return _comm.get_comm("main").scan(data, op, exclusive)
+    return host_scan(data, op, exclusive)
+
+
+def host_scan(data, op, exclusive=False, comm=None):
+    """scan of a host ndarray: RdcScan on "main", or RdcScanOn on the Comm
+    ``comm``."""
+    op = int(Op(op) if not isinstance(op, Op) else op)
+    if not isinstance(data, np.ndarray) or not data.flags.c_contiguous:
+        raise TypeError("scan takes a contiguous numpy.ndarray or a torch.Tensor")
+    if data.dtype not in DTYPE_ENUM__:
+        raise TypeError("data type %s not supported" % str(data.dtype))
+    ptr = data.ctypes.data_as(ctypes.c_void_p)
+    ex = 1 if exclusive else 0
+    if comm is not None:
+        check_call(_LIB.RdcScanOn(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], op, ex))
+    else:
+        check_call(_LIB.RdcScan(ptr, data.size, DTYPE_ENUM__[data.dtype], op, ex))
+    return data
+
+
 def allreduce_coalesced(arrays, op):
     """Bucketed allreduce of a list of arrays of one dtype, in place: the
     result of ``allreduce`` on each one (bit-identical), moved in fused device

@@ -421,6 +421,30 @@ void reduce_to_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, i
     c->Check(s);
 }
 
+// synchronous in-place scan / exscan of host or device memory on communicator c
+void scan_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, int dtype, int op, int exclusive) {
+    check_dtype_op(dtype, op);
+    if (exclusive != 0 && exclusive != 1)
+        throw std::invalid_argument("rdc: scan exclusive " + std::to_string(exclusive) + " outside {0, 1}");
+    if (c->size() == 1 || count == 0) return;
+    if (!sendrecv) throw std::invalid_argument("rdc: null buffer");
+    hipStream_t s = manager_stream(m, c->device());
+    if (is_device_pointer(sendrecv)) {
+        c->Scan(sendrecv, count, dtype, op, exclusive, s);
+        c->Check(s);
+        return;
+    }
+    // host buffer: the whole input up on every rank, the device scan, the whole
+    // result back on every rank but 0 — rank 0's host buffer is never written
+    const size_t esz = rdc_dtype_size(dtype);
+    if ((uintptr_t)sendrecv % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
+    char* d = static_cast<char*>(staging(m, std::max<size_t>(count * esz, 256), c->device()));
+    hcheck(hipMemcpyAsync(d, sendrecv, count * esz, hipMemcpyHostToDevice, s), "H2D");
+    c->Scan(d, count, dtype, op, exclusive, s);
+    if (c->rank() != 0) hcheck(hipMemcpyAsync(sendrecv, d, count * esz, hipMemcpyDeviceToHost, s), "D2H");
+    c->Check(s);
+}
+
 // synchronous coalesced allreduce of host or device buffers (all of one kind)
 void allreduce_coalesced_sync(Manager& m, Communicator* c, void** bufs, const size_t* counts, int nbuf, int dtype,
                               int op) {
@@ -749,6 +773,30 @@ int RdcReduceToOn(void* comm, void* sendrecv, size_t count, int dtype, int op, i
 
 int RdcCommReduceTo(void* comm, void* dev_buf, size_t count, int dtype, int op, int root, void* stream) {
     return guard([&] { as_comm(comm)->ReduceTo(dev_buf, count, dtype, op, root, static_cast<hipStream_t>(stream)); });
+}
+
+int RdcScan(void* sendrecv, size_t count, int dtype, int op, int exclusive) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] {
+        require_init(m);
+        check_dtype_op(dtype, op);
+        if (exclusive != 0 && exclusive != 1)
+            throw std::invalid_argument("rdc: scan exclusive " + std::to_string(exclusive) + " outside {0, 1}");
+        // world size 1: the buffer already holds its own prefix
+        if (m.world == 1 || count == 0) return;
+        scan_sync(m, get_comm(m, "main", true), sendrecv, count, dtype, op, exclusive);
+    });
+}
+
+int RdcScanOn(void* comm, void* sendrecv, size_t count, int dtype, int op, int exclusive) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] { scan_sync(m, as_comm(comm), sendrecv, count, dtype, op, exclusive); });
+}
+
+int RdcCommScan(void* comm, void* dev_buf, size_t count, int dtype, int op, int exclusive, void* stream) {
+    return guard([&] { as_comm(comm)->Scan(dev_buf, count, dtype, op, exclusive, static_cast<hipStream_t>(stream)); });
 }
 
 int RdcAllreduceCoalesced(void** bufs, const size_t* counts, int nbuf, int dtype, int op) {
@@ -1111,6 +1159,48 @@ int RdcPlanReduceTo(int n, int rank, int root, size_t count, int dtype, int op, 
         const Layout L = MakeLayout(n, scratch_bytes ? scratch_bytes : CommConfig().scratch_bytes);
         const std::vector<Piece> plan =
             PlanReduceTo(n, rank, root, count, esz, L, tile_bytes, max_blocks > 0 ? max_blocks : 256);
+        *out_pieces = (int)plan.size();
+        for (int k = 0; k < (int)plan.size() && k < max_pieces && out; ++k) {
+            uint64_t* o = out + (size_t)k * RDC_PLAN_WORDS;
+            const Piece& p = plan[(size_t)k];
+            o[0] = p.tile_bytes;
+            o[1] = (uint64_t)p.nb_scatter;
+            o[2] = (uint64_t)p.nb_reduce;
+            o[3] = (uint64_t)p.nb_gather;
+            for (int c = 0; c < RDC_MAX_RANKS; ++c) {
+                o[4 + c] = p.off[c];
+                o[20 + c] = p.len[c];
+                o[36 + c] = p.mis[c];
+                o[52 + c] = (uint64_t)p.tiles[c];
+            }
+        }
+    });
+}
+
+int RdcPlanScanBytes(int n, int rank, size_t count, int dtype, uint64_t* out5) {
+    return guard([&] {
+        const size_t esz = rdc_dtype_size(dtype);
+        if (n < 1 || n > RDC_MAX_RANKS || esz == 0 || !out5 || rank >= n) throw std::invalid_argument("rdc: bad argument");
+        const HbmBytes h = ModelScanBytes(n, rank, count, esz);
+        out5[0] = h.read_max;
+        out5[1] = h.write_max;
+        out5[2] = h.read_sum;
+        out5[3] = h.write_sum;
+        out5[4] = h.egress_max;
+    });
+}
+
+int RdcPlanScan(int n, int rank, size_t count, int dtype, int op, size_t scratch_bytes, size_t tile_bytes,
+                int max_blocks, uint64_t* out, int max_pieces, int* out_pieces) {
+    return guard([&] {
+        check_dtype_op(dtype, op);
+        const size_t esz = rdc_dtype_size(dtype);
+        if (n < 1 || n > RDC_MAX_RANKS || rank < 0 || rank >= n || esz == 0 || !out_pieces)
+            throw std::invalid_argument("rdc: bad argument");
+        if (tile_bytes % RDC_SLOT_ALIGN) throw std::invalid_argument("rdc: tile bytes must be a multiple of 256");
+        const Layout L = MakeLayout(n, scratch_bytes ? scratch_bytes : CommConfig().scratch_bytes);
+        std::vector<Piece> plan;
+        if (n > 1) plan = PlanScan(count, esz, L, tile_bytes, max_blocks > 0 ? max_blocks : 256);
         *out_pieces = (int)plan.size();
         for (int k = 0; k < (int)plan.size() && k < max_pieces && out; ++k) {
             uint64_t* o = out + (size_t)k * RDC_PLAN_WORDS;

@@ -1358,6 +1358,29 @@ void Communicator::ReduceTo(void* buf, size_t count, int dtype, int op, int root
     LaunchReduceTo(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, root, stream);
 }
 
+// The prefix reduction across ranks (MPI_Scan / MPI_Exscan), in place: rank r
+// ends with y[r] (inclusive) or, r > 0, y[r-1] (exclusive), where y[0] = x[0]
+// and y[q] = OP::Reduce(dst = y[q-1], src = x[q]) — a left fold in rank order,
+// element by element; rank 0's buffer is only read.  One schedule, on the
+// scratch path (k_scan); cfg_.ring_mincount is not consulted (the reference
+// has no scan, so no tree branch applies).  Everything is checked before the
+// first launch.
+void Communicator::Scan(void* buf, size_t count, int dtype, int op, int exclusive, hipStream_t stream) {
+    KernelSet ks;
+    if (!get_kernels(dtype, op, &ks))
+        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
+                                    std::to_string(op) + ")");
+    if (exclusive != 0 && exclusive != 1)
+        throw std::invalid_argument("rdc: scan exclusive " + std::to_string(exclusive) + " outside {0, 1}");
+    const size_t esz = rdc_dtype_size(dtype);
+    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
+    if (n_ == 1 || count == 0) return;
+    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ChannelCall call(ch_.get(), stream);
+    LaunchScan(ks, static_cast<char*>(buf), (uint64_t)count, esz, exclusive, stream);
+}
+
 // ------------------------------------------------- registered buffers ----
 // Every check here uses values identical on every rank (the schedule asked
 // for, the byte count, the channel kind, whether the stream is being
@@ -2363,6 +2386,46 @@ void Communicator::LaunchReduceTo(const KernelSet& ks, char* buf, const uint64_t
     trace_ = nullptr;  // rooted reduce launches are not traced
 }
 
+// The scan's schedule: PlanScan's launches of k_scan (pieces of at most one
+// slot, every block owning tiles blockIdx.x, + grid, ...), shaped like a ring
+// allreduce of `count * esz` bytes (RdcCommTune / RDC_NBLOCKS / RDC_TILE_BYTES
+// apply), the grid clamped by k_scan's own occupancy — the same clamp on every
+// rank, so every rank cuts the same tiles and every block of every rank is
+// resident.
+void Communicator::LaunchScan(const KernelSet& ks, char* buf, uint64_t count, size_t esz, int exclusive,
+                              hipStream_t stream) {
+    const uint64_t total = count * esz;
+    const Shape sh = ShapeFor(total, RDC_ALGO_RING);
+    const int grid_cap = LaunchGrid(sh.max_blocks > 0 ? sh.max_blocks : cus_min_, ks.occupancy(RDC_KIND_SCAN, n_));
+    const std::vector<Piece> plan = PlanScan(count, esz, layout(), sh.tile_bytes, grid_cap);
+    for (const Piece& p : plan) {
+        CollArgs a;
+        FillArgsCommon(&a);
+        if (&p == &plan.back()) {
+            a.notify = notify_;
+            a.notify_val = notify_val_;
+            notify_ = nullptr;
+        }
+        a.user = buf;
+        a.off[0] = p.off[0];
+        a.len[0] = p.len[0];
+        a.tiles[0] = p.tiles[0];
+        a.tile_bytes = p.tile_bytes;
+        a.pull = exclusive;
+        a.kind = RDC_KIND_SCAN;
+        ++seq_;
+        const int grid = p.nb_scatter;
+        last_launch_[0] = (uint64_t)grid;
+        last_launch_[1] = (uint64_t)grid;
+        last_launch_[2] = last_launch_[3] = 0;
+        last_launch_[4] = p.tile_bytes;
+        last_launch_[5] = RDC_LAUNCH_SCAN;
+        log_launch(this, seq_, RDC_LAUNCH_SCAN, total, grid, p.tile_bytes);
+        hip_check(ks.scan(a, grid, stream), "launch scan");
+    }
+    trace_ = nullptr;  // scan launches are not traced
+}
+
 // Staging image of the coalesced path, grown on demand (never shrinks).  The
 // old image is released stream-ordered (hipFreeAsync): launches already queued
 // may still read it, and a device-wide sync here would wait on kernels that
@@ -3101,7 +3164,7 @@ void Communicator::RaiseIfError(uint32_t e) const {
                                       "allgather (buffers) wait timed out",
                                       "a peer's hand-off belongs to another communicator's collective",
                                       "blocks of one launch read different launch numbers (RDC_SEQ_CHECK)",
-                                      "all-to-all wait timed out"};
+                                      "all-to-all wait timed out", "scan step wait timed out"};
         if (e == RDC_KERR_ORDER)
             throw std::runtime_error(std::string("rdc: device collective failed on rank ") + std::to_string(rank_) +
                                      ": " + names[e] +
@@ -3210,7 +3273,7 @@ void Communicator::RaiseIfError(uint32_t e) const {
             (void)hipGetLastError();
         }
         throw std::runtime_error(std::string("rdc: device collective failed on rank ") + std::to_string(rank_) +
-                                 ": " + (e < 9 ? names[e] : "unknown") +
+                                 ": " + (e < 10 ? names[e] : "unknown") +
                                  " (a peer did not join the collective; communicator is now unusable; this "
                                  "rank's last launch: " + (al < 6 ? algos[al] : "?") + ", grid " +
                                  std::to_string(last_launch_[0]) + ", tile " + std::to_string(last_launch_[4]) +

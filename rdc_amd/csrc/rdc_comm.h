@@ -243,6 +243,13 @@ public:
     // unsupported (dtype, op), a misaligned or null buffer.  root must be the
     // same on every rank.  n == 1 or count == 0: nothing is launched.
     void ReduceTo(void* buf, size_t count, int dtype, int op, int root, hipStream_t stream);
+    // In-place prefix reduction across ranks (MPI_Scan; exclusive = 1:
+    // MPI_Exscan), stream-ordered: rank r ends with y[r] (exclusive: r > 0 with
+    // y[r-1]), y[0] = x[0], y[q] = OP::Reduce(dst = y[q-1], src = x[q]); rank
+    // 0's buffer is only read.  Refused before any launch
+    // (std::invalid_argument): an unsupported (dtype, op), a misaligned or null
+    // buffer, exclusive outside {0, 1}.  n == 1 or count == 0: nothing is launched.
+    void Scan(void* buf, size_t count, int dtype, int op, int exclusive, hipStream_t stream);
     // bucketed allreduce: the result of Allreduce on every buffer in order
     // (bit-identical), moved as fused launches over a chunk-major staging image
     void AllreduceCoalesced(void* const* bufs, const size_t* counts, int nbuf, int dtype, int op,
@@ -456,6 +463,8 @@ private:
     // the scratch schedule of a rooted reduce (k_rooted) over chunk byte ranges of buf
     void LaunchReduceTo(const KernelSet& ks, char* buf, const uint64_t* off, const uint64_t* len, uint64_t total,
                         size_t esz, int root, hipStream_t stream);
+    // the scratch schedule of a scan / exscan (k_scan) over count elements of buf
+    void LaunchScan(const KernelSet& ks, char* buf, uint64_t count, size_t esz, int exclusive, hipStream_t stream);
     // one all-to-all launch over validated segments; equal_len: the equal split's bytes per peer
     // of this launch (PlanAlltoall's tile rule), 0 for alltoallv
     void LaunchAlltoall(const char* send, const uint64_t* send_off, const uint64_t* send_len, char* recv,

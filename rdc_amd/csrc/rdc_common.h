@@ -45,14 +45,19 @@ enum {
 // RDC_KIND_ALLTOALL: the personalised exchange (k_alltoall), the allgather's
 // slot protocol with a different segment per destination.
 // RDC_KIND_ROOTED: the reduction to one rank (k_rooted), the mesh's slots with
-// results going to the root only; ends like RDC_KIND_RSCATTER)
+// results going to the root only; ends like RDC_KIND_RSCATTER.
+// RDC_KIND_SCAN: the prefix reduction across ranks (k_scan), rank r folding
+// into rank r+1's RS slot r; ends like RDC_KIND_RSCATTER)
 enum { RDC_KIND_NONE = 0, RDC_KIND_MESH = 1, RDC_KIND_RING = 2, RDC_KIND_BCAST = 3, RDC_KIND_ALLGATHER = 4,
        RDC_KIND_ONESHOT = 5, RDC_KIND_TREE = 6, RDC_KIND_DIRECT = 7, RDC_KIND_RSCATTER = 8,
-       RDC_KIND_RSCATTER_DIRECT = 9, RDC_KIND_ALLTOALL = 10, RDC_KIND_ROOTED = 11 };
+       RDC_KIND_RSCATTER_DIRECT = 9, RDC_KIND_ALLTOALL = 10, RDC_KIND_ROOTED = 11,
+       RDC_KIND_SCAN = 12 };
 // RdcCommLastLaunch's algo word (and the RDC_LAUNCH_LOG kind) of an all-to-all
 // launch: not an allreduce schedule, so outside RDC_ALGO_* (broadcast logs 100,
 // allgather 101)
 #define RDC_LAUNCH_ALLTOALL 102
+// the same word of a scan / exscan launch
+#define RDC_LAUNCH_SCAN 103
 
 #define RDC_MAX_RANKS 16
 // 64-bit words from one hand-off flag to the next: 1 = packed (the default);
@@ -79,7 +84,8 @@ enum {
     RDC_KERR_ORDER = 6,
     // RDC_SEQ_CHECK: two blocks of one launch read different launch numbers
     RDC_KERR_SEQ = 7,
-    RDC_KERR_TIMEOUT_ALLTOALL = 8
+    RDC_KERR_TIMEOUT_ALLTOALL = 8,
+    RDC_KERR_TIMEOUT_SCAN = 9
 };
 
 static inline size_t rdc_dtype_size(int dtype) {
@@ -130,7 +136,8 @@ struct CollArgs {
     uint32_t* launch_kind;               // local: kind of the last completed launch
     uint32_t tag;                        // communicator's tag on its channel: bits 0-7 of every seq
     int kind;                            // this launch's RDC_KIND_*
-    int pull;                            // mesh: 1 = pull mode (RDC_ALGO_MESH_PULL, mesh_pull_body)
+    int pull;                            // mesh: 1 = pull mode (RDC_ALGO_MESH_PULL, mesh_pull_body);
+                                         //   scan: 1 = exclusive (rank r > 0 ends with y[r-1])
     int bcast_split;                     // broadcast: root -> forwarder per tile -> other ranks (n >= 3)
     uint64_t half_bytes;                 // one-shot: offset of the slot half used by odd seq
     uint64_t total_bytes;                // one-shot: whole buffer bytes

@@ -19,9 +19,11 @@ struct KernelSet {
     hipError_t (*rscatter_direct)(const CollArgs& a, int grid, hipStream_t s);  // registered buffers (k_rscatter_direct)
     // in-place reduction to rank a.root, every other rank's buffer untouched (k_rooted, scratch schedule)
     hipError_t (*rooted)(const CollArgs& a, int grid, hipStream_t s);
+    // in-place prefix reduction across ranks (Scan; a.pull = 1: Exscan), rank 0's buffer untouched (k_scan)
+    hipError_t (*scan)(const CollArgs& a, int grid, hipStream_t s);
     hipError_t (*svc)(const SvcArgs& a, hipStream_t s);  // the small-allreduce service (one block)
     // resident blocks per CU of the kernel a launch of `kind` (RDC_KIND_MESH /
-    // RING / ONESHOT / TREE / DIRECT / RSCATTER / RSCATTER_DIRECT / ROOTED) on n ranks uses (hipOccupancyMaxActiveBlocksPerMultiprocessor,
+    // RING / ONESHOT / TREE / DIRECT / RSCATTER / RSCATTER_DIRECT / ROOTED / SCAN) on n ranks uses (hipOccupancyMaxActiveBlocksPerMultiprocessor,
     // cached); the grid clamp of ResidentGrid (rdc_plan.h)
     int (*occupancy)(int kind, int n);
 };

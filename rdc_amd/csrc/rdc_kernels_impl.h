@@ -1103,6 +1103,122 @@ __device__ void ring_body(const CollArgs& a, uint64_t seq) {
     }
 }
 
+// ===================================================== prefix reduction ===
+// The scan's fold with two destinations, one pass over the tile:
+//   p = OP(recv, own)  — reducer(src = own, dst = the running prefix): the
+//                        prefix is always the dst operand;
+//   own  <- p (inclusive) or recv (exclusive);
+//   fwd  <- p, write-through (the next rank's RS slot; null on the last rank).
+// recv is this rank's RS slot, written by the previous rank: system-scope
+// loads.  recv and fwd are 16-B aligned (a piece's image starts at its slot's
+// base), so the 16-B body runs when own is 16-B aligned and every other
+// alignment goes element by element; both are exact.
+template <int OP, typename T>
+__device__ void block_scan_fold(char* own, const char* recv, char* fwd, uint64_t len, bool exclusive) {
+    const unsigned tid = threadIdx.x;
+    const bool push = fwd != nullptr;
+    auto fold_elem = [&](uint64_t e) {
+        T* d = reinterpret_cast<T*>(own + e);
+        const T y = ld_elem_sys<T>(recv + e);
+        const T p = OpF<OP>::apply(y, *d);
+        *d = exclusive ? y : p;
+        if (push) st_elem_wt<T>(fwd + e, p);
+    };
+    if ((((uintptr_t)own ^ (uintptr_t)recv) & 15) != 0) {  // buffer not 16-B aligned: element-wise
+        for (uint64_t e = (uint64_t)tid * sizeof(T); e < len; e += (uint64_t)kBlock * sizeof(T)) fold_elem(e);
+        return;
+    }
+    const uint64_t mis16 = (uint64_t)(uintptr_t)own & 15;
+    uint64_t head = mis16 ? 16 - mis16 : 0;
+    if (head > len) head = len;
+    const uint64_t nvec = (len - head) >> 4;
+    const uint64_t tail = head + (nvec << 4);
+    if (tid < head / sizeof(T)) fold_elem(tid * sizeof(T));
+    if (tid < (len - tail) / sizeof(T)) fold_elem(tail + tid * sizeof(T));
+    v4u* d = reinterpret_cast<v4u*>(own + head);
+    constexpr int U = 4;
+    for (uint64_t ib = 0; ib < nvec; ib += U * kBlock) {
+        const __amdgpu_buffer_rsrc_t rs = wt_rsrc(recv + head + ib * 16);
+        const __amdgpu_buffer_rsrc_t ws = wt_rsrc((push ? fwd : own) + head + ib * 16);  // dead without push
+        const uint64_t i = ib + tid;
+        if (ib + U * kBlock <= nvec) {
+            v4u x[U], y[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) x[u] = ld16(d + i + u * kBlock);
+#pragma unroll
+            for (int u = 0; u < U; ++u) y[u] = ld16_sys(rs, (uint32_t)((tid + u * kBlock) * 16));
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const v4u p = reduce16<OP, T>(y[u], x[u]);
+                st16(d + i + u * kBlock, exclusive ? y[u] : p);
+                if (push) st16_wt(ws, (uint32_t)((tid + u * kBlock) * 16), p);
+            }
+        } else {
+            for (int u = 0; u < U; ++u) {
+                if (i + u * kBlock >= nvec) break;
+                const v4u y = ld16_sys(rs, (uint32_t)((tid + u * kBlock) * 16));
+                const v4u p = reduce16<OP, T>(y, ld16(d + i + u * kBlock));
+                st16(d + i + u * kBlock, exclusive ? y : p);
+                if (push) st16_wt(ws, (uint32_t)((tid + u * kBlock) * 16), p);
+            }
+        }
+    }
+}
+
+// Scan / Exscan (MPI_Scan, MPI_Exscan), in place: rank r ends with y[r]
+// (inclusive) or y[r-1] (exclusive, a.pull = 1), y[0] = x[0], y[q] =
+// OP(dst = y[q-1], src = x[q]) — a left fold in rank order, per element, so
+// tiles and pieces cannot change a bit.  The ring's reduce step without the
+// wrap-around, pipelined tile by tile down the rank order: every block owns
+// tiles blockIdx.x, + gridDim.x, ... of the launch's bytes (off[0] / len[0] /
+// tiles[0]); for tile t rank 0 copies its bytes into rank 1's RS slot 0, rank
+// r > 0 waits for rank r-1's flag (row r-1, tile t), folds its RS slot r-1
+// with its own bytes, stores its result and — r < n-1 — the prefix into rank
+// r+1's RS slot r, then publishes rank r+1's flag (row r, tile t).  Rank 0's
+// buffer is only read.
+// Slot reuse: rank r writes owner r+1's RS slot r and flag
+// row r — a subset of what the mesh's scatter writes there, so it takes the
+// mesh's gate (after a one-shot: rank r+1's done word of the previous launch)
+// and no other.  Nothing returns to rank r from r+1, so like k_rscatter the
+// launch ends only after every peer's done word for it (launch_done<true>):
+// every slot has then been folded, and no successor needs a gate.
+// No deadlock: tile (r, t) depends on (r-1, t) and on this block's earlier
+// tiles only, every rank runs the same resident grid.
+template <int OP, typename T>
+__device__ void scan_body(const CollArgs& a, uint64_t seq) {
+    const int n = a.n, r = a.rank;
+    const bool fwd = r < n - 1;
+    const bool exclusive = a.pull != 0;
+    const int tiles = a.tiles[0];
+    if ((int)blockIdx.x >= tiles) return;
+    Abort ab{a.err, wall_clock64() + a.timeout_ticks, a.poll_rmw};
+    if (fwd && prev_kind(a) == RDC_KIND_ONESHOT && !gate_on_peers(a, seq, r + 1, 1, ab, RDC_KERR_TIMEOUT_SCAN)) return;
+    __shared__ uint64_t* s_flag[1];
+    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t toff = (uint64_t)t * a.tile_bytes;
+        uint64_t tlen = a.len[0] - toff;
+        if (tlen > a.tile_bytes) tlen = a.tile_bytes;
+        char* own = a.user + a.off[0] + toff;
+        char* out = fwd ? a.rs[r + 1] + (uint64_t)r * a.slot_bytes + toff : nullptr;
+        if (r == 0) {
+            block_copy<kDstPeer>(out, own, tlen);
+        } else {
+            if (threadIdx.x == 0) s_flag[0] = flag_word(a, r, (uint64_t)(r - 1) * a.max_tiles + t);
+            __syncthreads();
+            if (!block_wait(s_flag, 1, seq, ab, RDC_KERR_TIMEOUT_SCAN, a.uc)) return;
+            char* recv = a.rs[r] + (uint64_t)(r - 1) * a.slot_bytes + toff;
+            block_scan_fold<OP, T>(own, recv, out, tlen, exclusive);
+            // rank r-1 rewrites this range only in a later launch, which
+            // starts after this one's end (launch_done<true>)
+            if (a.poison) {
+                __syncthreads();
+                block_poison(recv, tlen);
+            }
+        }
+        if (fwd) block_publish1(flag_word(a, r + 1, (uint64_t)r * a.max_tiles + t), seq, a.uc);
+    }
+}
+
 // =================================================== one-shot allreduce ===
 // Small buffers: every rank pushes its WHOLE buffer into every peer's RS slot
 // `rank` (one hand-off instead of the mesh's two), then folds all n
@@ -1526,6 +1642,14 @@ template <int OP, typename T, int NMAX>
 __global__ __launch_bounds__(kBlock) void k_rooted(CollArgs a) {
     uint64_t seq;
     if (!launch_begin(a, &seq)) rooted_body<OP, T, NMAX>(a, seq);
+    launch_done<true>(a, seq);
+}
+
+// prefix reduction across ranks, scratch schedule (RDC_KIND_SCAN)
+template <int OP, typename T>
+__global__ __launch_bounds__(kBlock) void k_scan(CollArgs a) {
+    uint64_t seq;
+    if (!launch_begin(a, &seq)) scan_body<OP, T>(a, seq);
     launch_done<true>(a, seq);
 }
 
@@ -1991,6 +2115,10 @@ struct Kernels {
         hipLaunchKernelGGL((k_ring<OP, T>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
         return hipGetLastError();
     }
+    static hipError_t scan(const CollArgs& a, int grid, hipStream_t s) {
+        hipLaunchKernelGGL((k_scan<OP, T>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
+        return hipGetLastError();
+    }
     static hipError_t svc(const SvcArgs& a, hipStream_t s) {
         const bool hx = a.hx != nullptr;
         if (a.n <= 8 && hx)
@@ -2012,9 +2140,9 @@ struct Kernels {
     }
     static int occupancy(int kind, int n) {
         // [mesh 8, mesh 16, oneshot 8, oneshot 16, ring, tree 8, tree 16, direct 8, direct 16,
-        //  rscatter 8, rscatter 16, rscatter direct 8, rscatter direct 16, rooted 8, rooted 16];
+        //  rscatter 8, rscatter 16, rscatter direct 8, rscatter direct 16, rooted 8, rooted 16, scan];
         // 0 = not queried yet
-        static int cache[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        static int cache[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         const int wide = n > 8 ? 1 : 0;
         const int slot = kind == RDC_KIND_RING      ? 4
                          : kind == RDC_KIND_TREE    ? 5 + wide
@@ -2023,6 +2151,7 @@ struct Kernels {
                          : kind == RDC_KIND_RSCATTER ? 9 + wide
                          : kind == RDC_KIND_RSCATTER_DIRECT ? 11 + wide
                          : kind == RDC_KIND_ROOTED  ? 13 + wide
+                         : kind == RDC_KIND_SCAN    ? 15
                                                     : wide;
         if (cache[slot] > 0) return cache[slot];
         int b = 0;
@@ -2042,6 +2171,7 @@ struct Kernels {
             case 12: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter_direct<OP, T, 16>, kBlock, debug_lds_pad()); break;
             case 13: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rooted<OP, T, 8>, kBlock, debug_lds_pad()); break;
             case 14: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rooted<OP, T, 16>, kBlock, debug_lds_pad()); break;
+            case 15: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_scan<OP, T>, kBlock, debug_lds_pad()); break;
             default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_ring<OP, T>, kBlock, debug_lds_pad()); break;
         }
         if (e != hipSuccess || b <= 0) {
@@ -2062,6 +2192,7 @@ struct Kernels {
     ks->rscatter = &Kernels<OP, T>::rscatter; \
     ks->rscatter_direct = &Kernels<OP, T>::rscatter_direct; \
     ks->rooted = &Kernels<OP, T>::rooted; \
+    ks->scan = &Kernels<OP, T>::scan;     \
     ks->oneshot = &Kernels<OP, T>::oneshot; \
     ks->tree = &Kernels<OP, T>::tree;       \
     ks->svc = &Kernels<OP, T>::svc;         \

@@ -198,6 +198,34 @@ std::vector<Piece> PlanReduceTo(int n, int rank, int root, uint64_t count, size_
     return PlanReduceToRanges(n, rank, root, off, len, esz, L, cfg_tile, max_blocks, split);
 }
 
+std::vector<Piece> PlanScan(uint64_t count, size_t esz, const Layout& L, size_t cfg_tile, int max_blocks) {
+    std::vector<Piece> out;
+    if (count == 0 || esz == 0) return out;
+    const uint64_t total = count * esz;
+    const size_t G = (size_t)std::max(1, max_blocks);
+    const size_t cfg = cfg_tile ? round_up(cfg_tile, RDC_SLOT_ALIGN) : 0;
+    // a piece fits one slot and one flag row; both bounds are multiples of 256,
+    // so of every element size.  The automatic tile is at least 64 KiB, where
+    // one slot's tiles always fit the row (max_tiles counts 16 KiB tiles)
+    uint64_t cap = AlltoallCap(L);
+    if (cfg) cap = std::min<uint64_t>(cap, (uint64_t)L.max_tiles * cfg);
+    for (uint64_t off = 0; off < total; off += cap) {
+        Piece p;
+        memset(&p, 0, sizeof(p));
+        p.off[0] = off;
+        p.len[0] = std::min<uint64_t>(cap, total - off);
+        size_t t = cfg;
+        if (t == 0)
+            t = std::min<size_t>(std::max<size_t>(round_up((p.len[0] + G - 1) / G, RDC_SLOT_ALIGN), (size_t)64 << 10),
+                                 (size_t)1 << 20);
+        p.tile_bytes = t;
+        p.tiles[0] = (int)((p.len[0] + t - 1) / t);
+        p.nb_scatter = (int)std::min<size_t>((size_t)p.tiles[0], G);
+        out.push_back(p);
+    }
+    return out;
+}
+
 uint64_t OneshotHalfBytes(const Layout& L) { return round_down(L.slot_bytes / 2, RDC_SLOT_ALIGN); }
 
 bool OneshotEligible(int n, uint64_t bytes, const Layout& L, uint64_t push_max) {
@@ -675,6 +703,30 @@ HbmBytes ModelReduceToBytes(int n, int rank, int root, uint64_t count, size_t es
         } else {
             eg += own;
         }
+        h.read_max = std::max(h.read_max, rd);
+        h.write_max = std::max(h.write_max, wr);
+        h.read_sum += rd;
+        h.write_sum += wr;
+        h.egress_max = std::max(h.egress_max, eg);
+    }
+    return h;
+}
+
+// One scan / exscan on rank `rank`, in the same conventions, per the loops of
+// k_scan (S = the buffer's bytes):
+//   rank 0:        load user, store rank 1's slot (remote: egress)
+//   0 < r < n-1:   load own slot + user, store user + rank r+1's slot (egress)
+//   rank n-1:      load own slot + user, store user
+// rank < 0: the maxima and sums over all ranks.
+HbmBytes ModelScanBytes(int n, int rank, uint64_t count, size_t esz) {
+    HbmBytes h;
+    if (n < 2 || count == 0) return h;
+    const uint64_t S = count * esz;
+    for (int r = 0; r < n; ++r) {
+        if (rank >= 0 && r != rank) continue;
+        const uint64_t rd = r == 0 ? S : 2 * S;
+        const uint64_t wr = (r == 0 || r == n - 1) ? S : 2 * S;
+        const uint64_t eg = r == n - 1 ? 0 : S;
         h.read_max = std::max(h.read_max, rd);
         h.write_max = std::max(h.write_max, wr);
         h.read_sum += rd;

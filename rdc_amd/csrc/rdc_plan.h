@@ -198,6 +198,17 @@ std::vector<Piece> PlanReduceToRanges(int n, int rank, int root, const uint64_t*
 std::vector<Piece> PlanReduceTo(int n, int rank, int root, uint64_t count, size_t esz, const Layout& L,
                                 size_t cfg_tile, int max_blocks, MeshSplit split = MeshSplit());
 
+// ---------------------------------------------------- prefix reduction ---
+// Scan / Exscan (Communicator::Scan): the launches of k_scan, the same on every
+// rank.  Each piece uses off[0] / len[0] / tiles[0], its image starts at its
+// slot's base (mis = 0) and nb_scatter is its grid, min(tiles, max_blocks).  A
+// piece has at most min(AlltoallCap(L), max_tiles x tile) bytes, so any size
+// runs, as several launches.  Tile bytes depend only on values equal on every
+// rank — cfg_tile (rounded up to 256; no 16 KiB floor), else the piece's bytes
+// / max_blocks rounded up to 256 and kept within [64 KiB, 1 MiB] — so both
+// ends of every hand-off cut alike.
+std::vector<Piece> PlanScan(uint64_t count, size_t esz, const Layout& L, size_t cfg_tile, int max_blocks);
+
 // ------------------------------------------------------ tree allreduce ---
 // rdc_reduce_ring_mincount (communicator_manager.cc:46): TryAllreduce takes
 // TryAllreduceTree for buffers of at most that many bytes
@@ -267,6 +278,10 @@ HbmBytes ModelReduceScatterBytes(int n, uint64_t count, size_t esz, int algo);
 // AG slots and stores the gathered chunks; a non-root rank's result store is
 // remote: egress).  rank < 0: the maxima and sums over all n ranks
 HbmBytes ModelReduceToBytes(int n, int rank, int root, uint64_t count, size_t esz);
+// The same model of one scan / exscan of S bytes on rank `rank`: rank 0 loads
+// S and stores S remotely; 0 < r < n-1 loads 2 S and stores 2 S, one of them
+// remotely; rank n-1 loads 2 S and stores S.  rank < 0: the maxima and sums
+HbmBytes ModelScanBytes(int n, int rank, uint64_t count, size_t esz);
 // The same model of one all-to-all on rank `rank` (one rank's row send_len and
 // column recv_len of the size matrix, so max = sum = this rank's bytes):
 // reads = the send buffer + this rank's own slots, writes = the peers' slots

@@ -34,6 +34,16 @@ rooted reduce's modelled HBM bytes (read + write, summed over the ranks) over
 the mesh allreduce's (RdcPlanReduceToBytes / RdcPlanHbmBytes), and
 reduce_to_hbm_fraction = those bytes per pipelined call over the HBM peak (the
 ranks share one GPU).
+SWEEP_COLLECTIVE=scan times RdcCommScan (inclusive) and, on the same
+communicator and buffer, the same prefix built from what a caller had before it
+(Comm.recv from rank r-1, RdcReduce, Comm.send to rank r+1: "composed") and the
+ring allreduce (algo 1) of the same bytes as the scale, in alternating rounds
+(SWEEP_ROUNDS, default 5).  The two collectives are timed pipelined (<name>) and
+synchronised per call (<name>_sync); the composed form completes every call by
+construction.  Per form the median over rounds of the slowest rank's time per
+call and the spread.  Next to them scan_hbm_fraction = the scan's modelled HBM
+bytes (RdcPlanScanBytes, read + write, summed over the ranks: they share one
+GPU) per pipelined call over the HBM peak.
 
     python -m torch.distributed.run --nproc-per-node N tools/algo_sweep.py [sizes_MiB] [steps]
 """
@@ -210,6 +220,86 @@ def reduce_to_sweep(sizes, steps, rank, world, comm, sp):
                           "rounds": rounds, "ranks_share_gpu": True, "hbm_peak_bytes_per_s": HBM_PEAK}), flush=True)
 
 
+def scan_sweep(sizes, steps, rank, world, comm, sp):
+    """Per size, `rounds` rounds alternating the three forms on one buffer; a
+    round's time is the slowest rank's, the figure the median over rounds."""
+    import torch
+    import torch.distributed as dist
+    import rdc_amd
+    from rdc_amd._lib import _LIB, check_call
+    rounds = int(os.environ.get("SWEEP_ROUNDS", "5"))
+    big = int(max(sizes) * (1 << 20))
+    buf = torch.empty(big // 4, dtype=torch.float32, device="cuda")
+    tmp = torch.empty(big // 4, dtype=torch.float32, device="cuda")
+    p, q = ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(tmp.data_ptr())
+    out = {}
+    for mib in sizes:
+        nb = int(mib * (1 << 20))
+        rdc_amd.fill_(buf, 0x5EED0000, rank)   # sums of sums overflow after enough calls: fresh values per size
+
+        def scan():
+            check_call(_LIB.RdcCommScan(comm.handle, p, nb // 4, 6, 2, 0, sp))
+
+        def ring():
+            check_call(_LIB.RdcCommAllreduceEx(comm.handle, p, nb // 4, 6, 2, 1, sp))
+
+        def composed():  # the same prefix as a user of the parent commit writes it
+            if rank > 0:
+                comm.recv(tmp[: nb // 4], rank - 1)
+                check_call(_LIB.RdcReduce(p, q, nb // 4, 6, 2, sp))
+            if rank < world - 1:
+                comm.send(buf[: nb // 4], rank + 1)
+
+        def timed(fn, n_steps, sync):
+            torch.cuda.synchronize()
+            dist.barrier()
+            t0 = time.perf_counter()
+            for _ in range(n_steps):
+                fn()
+                if sync:
+                    torch.cuda.synchronize()
+            torch.cuda.synchronize()
+            t = torch.tensor([(time.perf_counter() - t0) / n_steps], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            return float(t[0])
+
+        n_steps = max(steps, min(500, int(2e8 // max(nb, 1))))
+        n_comp = max(3, min(steps, int(5e7 // max(nb * (world - 1), 1))))
+        for fn in (scan, ring):
+            for _ in range(3):
+                fn()
+        composed()
+        comm.check(sp)
+        ts = {}
+        for _ in range(rounds):
+            for name, fn in (("scan", scan), ("allreduce_ring", ring)):
+                ts.setdefault(name, []).append(timed(fn, n_steps, False))
+                ts.setdefault(name + "_sync", []).append(timed(fn, min(n_steps, 100), True))
+            ts.setdefault("composed", []).append(timed(composed, n_comp, True))
+        comm.check(sp)
+        row = {}
+        for name, v in ts.items():
+            v.sort()
+            med = v[len(v) // 2]
+            row[name] = round(med * 1e3, 4)
+            row[name + "_spread"] = round((v[-1] - v[0]) / med, 3)
+        ll = (ctypes.c_uint64 * 6)()
+        scan()
+        check_call(_LIB.RdcCommLastLaunch(comm.handle, ll))
+        comm.check(sp)
+        row["scan_grid_tile"] = [int(ll[0]), int(ll[4])]
+        m = (ctypes.c_uint64 * 5)()
+        check_call(_LIB.RdcPlanScanBytes(world, -1, nb // 4, 6, m))
+        row["scan_hbm_fraction"] = round((m[2] + m[3]) / (row["scan"] * 1e-3) / HBM_PEAK, 4)
+        row["speedup_vs_composed"] = round(row["composed"] / row["scan_sync"], 2)   # both complete every call
+        row["scan_over_ring"] = round(row["scan"] / row["allreduce_ring"], 3)
+        row["scan_over_ring_sync"] = round(row["scan_sync"] / row["allreduce_ring_sync"], 3)
+        out["%g MiB" % mib] = row
+    if rank == 0:
+        print(json.dumps({"algo_sweep_ms_per_call": out, "world": world, "collective": "scan", "rounds": rounds,
+                          "ranks_share_gpu": True, "hbm_peak_bytes_per_s": HBM_PEAK}), flush=True)
+
+
 def main():
     sizes = [float(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "1,4,16,64,256").replace("/", ",").split(",")]
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -230,6 +320,11 @@ def main():
         return
     if os.environ.get("SWEEP_COLLECTIVE", "allreduce") == "reduce_to":
         reduce_to_sweep(sizes, steps, rank, world, comm, sp)
+        dist.barrier()
+        rdc_amd.finalize()
+        return
+    if os.environ.get("SWEEP_COLLECTIVE", "allreduce") == "scan":
+        scan_sweep(sizes, steps, rank, world, comm, sp)
         dist.barrier()
         rdc_amd.finalize()
         return
