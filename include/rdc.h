@@ -41,9 +41,36 @@ namespace rdc {
 /*! \brief name of the default communicator (include/comm/communicator.h:21) */
 static const std::string kMainCommName = "main";
 
+/*! \brief a (value, index) pair for op::MaxLoc / op::MinLoc (MI355X addition;
+ *  MPI_FLOAT_INT / MPI_2INT): "which rank holds the best candidate, and where".
+ *  8 bytes, 8-byte aligned (the library refuses a pair buffer that is only
+ *  4-byte aligned), V = float or int32_t.  There is no 16-byte
+ *  { double, int64 } pair. */
+template <typename V>
+struct alignas(8) ValueIndex {
+    static_assert(std::is_same<V, float>::value || std::is_same<V, int32_t>::value,
+                  "rdc::ValueIndex<V>: V is float or int32_t");
+    V value;
+    int32_t index;
+};
+static_assert(sizeof(ValueIndex<float>) == 8 && alignof(ValueIndex<float>) == 8 &&
+                  std::is_trivially_copyable<ValueIndex<float>>::value,
+              "rdc::ValueIndex<float> is the 8-byte element of dtype 12");
+static_assert(sizeof(ValueIndex<int32_t>) == 8 && alignof(ValueIndex<int32_t>) == 8 &&
+                  std::is_trivially_copyable<ValueIndex<int32_t>>::value,
+              "rdc::ValueIndex<int32_t> is the 8-byte element of dtype 13");
+
 namespace mpi {
 /*! \brief reduction operators (include/core/mpi.h:12-17) */
-enum OpType { kMax = 0, kMin = 1, kSum = 2, kBitwiseOR = 3 };
+enum OpType {
+    kMax = 0,
+    kMin = 1,
+    kSum = 2,
+    kBitwiseOR = 3,
+    /*! \brief MI355X additions (MPI_MAXLOC / MPI_MINLOC) over ValueIndex<V> */
+    kMaxLoc = 4,
+    kMinLoc = 5
+};
 /*! \brief element types (include/core/mpi.h:19-30) */
 enum DataType {
     kChar = 0,
@@ -55,7 +82,10 @@ enum DataType {
     kFloat = 6,
     kDouble = 7,
     kLongLong = 8,
-    kULongLong = 9
+    kULongLong = 9,
+    /*! \brief MI355X additions: ValueIndex<float>, ValueIndex<int32_t> (MPI_FLOAT_INT / MPI_2INT) */
+    kFloatInt = 12,
+    kIntInt = 13
 };
 template <typename DType>
 inline DataType GetType(void);
@@ -70,7 +100,23 @@ template <> inline DataType GetType<float>(void) { return kFloat; }
 template <> inline DataType GetType<double>(void) { return kDouble; }
 template <> inline DataType GetType<long long>(void) { return kLongLong; }              // NOLINT
 template <> inline DataType GetType<unsigned long long>(void) { return kULongLong; }    // NOLINT
+template <> inline DataType GetType<ValueIndex<float>>(void) { return kFloatInt; }
+template <> inline DataType GetType<ValueIndex<int32_t>>(void) { return kIntInt; }
 }  // namespace mpi
+
+namespace detail {
+template <typename T> struct IsValueIndex : std::false_type {};
+template <typename V> struct IsValueIndex<ValueIndex<V>> : std::true_type {};
+/*! \brief MaxLoc / MinLoc fold ValueIndex<V> and nothing else folds it: a
+ *  mismatch (Allreduce<op::Sum, ValueIndex<float>>, Allreduce<op::MaxLoc,
+ *  float>) does not compile */
+template <typename OP, typename DType> struct CheckOpType {
+    static const bool kLoc = OP::kType == mpi::kMaxLoc || OP::kType == mpi::kMinLoc;
+    static_assert(kLoc == IsValueIndex<DType>::value,
+                  "rdc: op::MaxLoc / op::MinLoc go with rdc::ValueIndex<V> elements, and only they do");
+    static const bool value = true;
+};
+}  // namespace detail
 
 /*! \brief reduction operators (include/core/mpi.h:84-120).  kType names the
  *  device kernel the typed collectives launch; Reduce(dst, src) is the
@@ -103,6 +149,25 @@ struct BitOR {
     static const mpi::OpType kType = mpi::kBitwiseOR;
     template <typename DType> inline static void Reduce(DType& dst, const DType& src) {  // NOLINT(*)
         dst |= src;
+    }
+};
+/*! \brief MI355X additions (MPI_MAXLOC / MPI_MINLOC) over ValueIndex<V>:
+ *  dst = src when dst.value < src.value (MinLoc: >), or when the values are
+ *  equal and src.index < dst.index.  So a NaN in dst.value stays and a NaN in
+ *  src.value is ignored, as for Max / Min; -0.0f == +0.0f is a tie in value
+ *  and the lower index wins; on a full tie (equal value, equal index) dst
+ *  stays whole, value bits included, so a +0 / -0 pair with equal indexes
+ *  depends on the operand order, as NaN does for Max. */
+struct MaxLoc {
+    static const mpi::OpType kType = mpi::kMaxLoc;
+    template <typename V> inline static void Reduce(ValueIndex<V>& dst, const ValueIndex<V>& src) {  // NOLINT(*)
+        if (dst.value < src.value || (dst.value == src.value && src.index < dst.index)) dst = src;
+    }
+};
+struct MinLoc {
+    static const mpi::OpType kType = mpi::kMinLoc;
+    template <typename V> inline static void Reduce(ValueIndex<V>& dst, const ValueIndex<V>& src) {  // NOLINT(*)
+        if (dst.value > src.value || (dst.value == src.value && src.index < dst.index)) dst = src;
     }
 };
 /*! \brief dst[i] = OP::Reduce(dst[i], src[i]) for i < len, on HOST memory, in
@@ -647,6 +712,7 @@ inline std::unique_ptr<comm::ICommunicator> CreateGroup(const std::vector<int>& 
 /*! \brief in-place allreduce (include/api.h:62-64, rdc-inl.h:125-135) */
 template <typename OP, typename DType>
 inline void Allreduce(DType* sendrecvbuf, uint64_t count, const std::string& comm_name = kMainCommName) {
+    static_assert(detail::CheckOpType<OP, DType>::value, "");
     if (GetWorldSize() == 1 || count == 0) return;  // communicator_base.h:133-138
     GetCommunicator(comm_name)->Allreduce(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType);
 }
@@ -660,6 +726,7 @@ inline void Allreduce(DType* sendrecvbuf, uint64_t count, const std::string& com
 template <typename OP, typename DType>
 inline std::pair<uint64_t, uint64_t> ReduceScatter(DType* sendrecvbuf, uint64_t count,
                                                    const std::string& comm_name = kMainCommName) {
+    static_assert(detail::CheckOpType<OP, DType>::value, "");
     if (GetWorldSize() == 1 || count == 0) return std::pair<uint64_t, uint64_t>(0, count);
     comm::ICommunicator* c = GetCommunicator(comm_name);
     c->ReduceScatter(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType);
@@ -678,6 +745,7 @@ inline std::pair<uint64_t, uint64_t> ReduceScatter(DType* sendrecvbuf, uint64_t 
  *  launched */
 template <typename OP, typename DType>
 inline void ReduceTo(DType* sendrecvbuf, uint64_t count, int root, const std::string& comm_name = kMainCommName) {
+    static_assert(detail::CheckOpType<OP, DType>::value, "");
     GetCommunicator(comm_name)->ReduceTo(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType, root);
 }
 
@@ -688,6 +756,7 @@ inline void ReduceTo(DType* sendrecvbuf, uint64_t count, int root, const std::st
  *  result does not have Allreduce's ring-order bits */
 template <typename OP, typename DType>
 inline void Scan(DType* sendrecvbuf, uint64_t count, const std::string& comm_name = kMainCommName) {
+    static_assert(detail::CheckOpType<OP, DType>::value, "");
     GetCommunicator(comm_name)->Scan(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType, false);
 }
 
@@ -696,6 +765,7 @@ inline void Scan(DType* sendrecvbuf, uint64_t count, const std::string& comm_nam
  *  passed (MPI leaves it undefined) */
 template <typename OP, typename DType>
 inline void Exscan(DType* sendrecvbuf, uint64_t count, const std::string& comm_name = kMainCommName) {
+    static_assert(detail::CheckOpType<OP, DType>::value, "");
     GetCommunicator(comm_name)->Scan(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType, true);
 }
 
@@ -751,6 +821,7 @@ inline void Allreduce(Buffer& sendrecvbuf, const std::string& comm_name = kMainC
 template <typename OP, typename DType>
 inline void AllreduceCoalesced(DType** bufs, const uint64_t* counts, int nbuf,
                                const std::string& comm_name = kMainCommName) {
+    static_assert(detail::CheckOpType<OP, DType>::value, "");
     if (GetWorldSize() == 1 || nbuf == 0) return;
     std::vector<size_t> c((size_t)nbuf);
     for (int b = 0; b < nbuf; ++b) c[(size_t)b] = (size_t)counts[b];

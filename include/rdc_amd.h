@@ -16,9 +16,28 @@
  *   - dtype: mpi::DataType (include/core/mpi.h:19-30) = rdc/core.py:160-169:
  *       0 int8, 1 uint8, 2 int32, 3 uint32, 4 int64, 5 uint64, 6 float32,
  *       7 float64, 8 long long, 9 unsigned long long
- *     MI355X additions: 10 float16 (IEEE binary16), 11 bfloat16.
+ *     MI355X additions: 10 float16 (IEEE binary16), 11 bfloat16, and the
+ *     (value, index) pairs of MAXLOC / MINLOC, 8 bytes, the value first:
+ *       12 F32_I32 { float value; int32_t index; }
+ *       13 I32_I32 { int32_t value; int32_t index; }
+ *     A buffer of pairs must be 8-byte aligned.  The C struct alone guarantees
+ *     4 (declare it alignas(8), as rdc::ValueIndex<V> is): a 4-byte aligned
+ *     pair buffer is refused as "not aligned to its element size".  There is no
+ *     16-byte { double, int64 } pair.
  *   - op: mpi::OpType (include/core/mpi.h:12-17) = rdc/core.py:16-20:
  *       0 MAX, 1 MIN, 2 SUM, 3 BITOR (integer dtypes only)
+ *     MI355X additions (MPI_MAXLOC / MPI_MINLOC): 4 MAXLOC, 5 MINLOC.
+ *       MAXLOC: dst = src when dst.value < src.value ||
+ *                             (dst.value == src.value && src.index < dst.index)
+ *       MINLOC: the same with > in the first comparison.
+ *     So: a NaN in dst.value stays and a NaN in src.value is ignored, as for
+ *     MAX / MIN; -0.0f == +0.0f is a tie in value and the lower index wins; on
+ *     a full tie (equal value, equal index) dst stays whole, value bits
+ *     included, so a +0 / -0 pair with equal indexes depends on the operand
+ *     order, as NaN does for MAX.  MAXLOC / MINLOC are valid with dtypes 12 /
+ *     13 only, and those dtypes with MAXLOC / MINLOC only: every other
+ *     combination is refused before anything is launched, the message naming
+ *     both.  RdcFill refuses the pair dtypes (upload the inputs).
  *   - results are bit-identical to the reference's CPU ring allreduce
  *     (src/comm/communicator_collective.cc:115-203) on the same inputs.
  */

@@ -56,6 +56,30 @@ _ALGOS = {"auto": ALGO_AUTO, "ring": ALGO_RING, "mesh": ALGO_MESH, "oneshot": AL
           "mesh_pull": ALGO_MESH_PULL, "direct": ALGO_DIRECT}
 
 
+_OP_LOC = (4, 5)  # Op.MAXLOC, Op.MINLOC
+_PAIR_CODES = {"float32": 12, "int32": 13}  # value type -> F32_I32 / I32_I32
+
+
+def _elem_args(tensor, op, value):
+    """``(element count, dtype code)`` of a tensor argument.  torch has no
+    struct dtype, so Op.MAXLOC / Op.MINLOC take their (value, index) pairs as
+    a ``torch.int32`` tensor whose last dimension is 2 (``pack_pairs``), the
+    value's bits first; ``value`` ("float32", the default, or "int32") says how
+    to read them.  Anything else raises TypeError before the library is called."""
+    if int(op) in _OP_LOC:
+        import torch
+        if tensor.dtype != torch.int32 or tensor.dim() < 1 or tensor.shape[-1] != 2:
+            raise TypeError("rdc_amd: MAXLOC / MINLOC take a torch.int32 tensor whose last dimension is 2 "
+                            "(value bits, index), got %s %s" % (tensor.dtype, tuple(tensor.shape)))
+        v = "float32" if value is None else value
+        if v not in _PAIR_CODES:
+            raise TypeError("rdc_amd: value must be \"float32\" or \"int32\", got %r" % (value,))
+        return tensor.numel() // 2, _PAIR_CODES[v]
+    if value is not None:
+        raise TypeError("rdc_amd: value= goes with Op.MAXLOC / Op.MINLOC only")
+    return tensor.numel(), _dev.dtype_enum(tensor.dtype)
+
+
 def _a2a_equal_counts(nsend, nrecv, n):
     if nsend != nrecv or nsend % n:
         raise ValueError("rdc_amd: all_to_all needs send and recv of one size divisible by the world size")
@@ -109,22 +133,26 @@ class Comm(object):
     def alloc_kind(self):
         return _LIB.RdcCommAllocKind(self.handle)
 
-    def allreduce(self, tensor, op, algo="auto", stream=None):
+    def allreduce(self, tensor, op, algo="auto", stream=None, value=None):
         """In-place allreduce of a contiguous ROCm tensor on this
         communicator; returns it.  A numpy array takes rdc.allreduce's host
         path and copy rule (rdc/core.py:196-217) on this communicator
         (rdc::Allreduce<OP>(buf, count, comm_name), include/api.h:62-64) and
-        returns the reduced flat array."""
+        returns the reduced flat array.  Op.MAXLOC / Op.MINLOC: an int32
+        tensor of (value bits, index) pairs, last dimension 2, read as
+        ``value`` = "float32" (default) or "int32" (``_elem_args``); so for
+        reduce_scatter, reduce, scan and allreduce_coalesced."""
         if not _is_tensor(tensor):
             from .core import host_allreduce
             return host_allreduce(tensor, op, comm=self.handle)
+        count, dtype = _elem_args(tensor, op, value)
         _dev._check_tensor(tensor)
         s = stream if stream is not None else _dev.current_stream_ptr(tensor.device)
-        check_call(_LIB.RdcCommAllreduceEx(self.handle, ctypes.c_void_p(tensor.data_ptr()), tensor.numel(),
-                                           _dev.dtype_enum(tensor.dtype), int(op), _ALGOS[algo], s))
+        check_call(_LIB.RdcCommAllreduceEx(self.handle, ctypes.c_void_p(tensor.data_ptr()), count,
+                                           dtype, int(op), _ALGOS[algo], s))
         return tensor
 
-    def reduce_scatter(self, tensor, op, algo="auto", stream=None):
+    def reduce_scatter(self, tensor, op, algo="auto", stream=None, value=None):
         """In-place reduce-scatter of a contiguous ROCm tensor (RdcCommReduceScatter;
         TryReduceScatterRing, communicator_collective.cc:115-182): chunk ``rank``
         of ``split_range(tensor.numel(), world_size, rank)`` receives the
@@ -135,14 +163,17 @@ class Comm(object):
         from .core import host_reduce_scatter, split_range
         if not _is_tensor(tensor):
             return host_reduce_scatter(tensor, op, comm=self)
+        count, dtype = _elem_args(tensor, op, value)
         _dev._check_tensor(tensor)
         s = stream if stream is not None else _dev.current_stream_ptr(tensor.device)
-        check_call(_LIB.RdcCommReduceScatter(self.handle, ctypes.c_void_p(tensor.data_ptr()), tensor.numel(),
-                                             _dev.dtype_enum(tensor.dtype), int(op), _ALGOS[algo], s))
-        lo, hi = split_range(tensor.numel(), self.world_size, self.rank)
+        check_call(_LIB.RdcCommReduceScatter(self.handle, ctypes.c_void_p(tensor.data_ptr()), count,
+                                             dtype, int(op), _ALGOS[algo], s))
+        lo, hi = split_range(count, self.world_size, self.rank)
+        if int(op) in _OP_LOC:
+            return tensor.view(-1, 2)[lo:hi]
         return tensor.view(-1)[lo:hi]
 
-    def reduce(self, tensor, op, root, stream=None):
+    def reduce(self, tensor, op, root, stream=None, value=None):
         """In-place reduction of a contiguous ROCm tensor to rank ``root``
         (RdcCommReduceTo; MPI_Reduce): on ``root`` the tensor receives the
         reduction, with the bits ``allreduce`` puts there by the ring order, at
@@ -153,13 +184,14 @@ class Comm(object):
         from .core import host_reduce
         if not _is_tensor(tensor):
             return host_reduce(tensor, op, root, comm=self)
+        count, dtype = _elem_args(tensor, op, value)
         _dev._check_tensor(tensor)
         s = stream if stream is not None else _dev.current_stream_ptr(tensor.device)
-        check_call(_LIB.RdcCommReduceTo(self.handle, ctypes.c_void_p(tensor.data_ptr()), tensor.numel(),
-                                        _dev.dtype_enum(tensor.dtype), int(op), int(root), s))
+        check_call(_LIB.RdcCommReduceTo(self.handle, ctypes.c_void_p(tensor.data_ptr()), count,
+                                        dtype, int(op), int(root), s))
         return tensor
 
-    def scan(self, tensor, op, exclusive=False, stream=None):
+    def scan(self, tensor, op, exclusive=False, stream=None, value=None):
         """In-place prefix reduction of a contiguous ROCm tensor across ranks
         (RdcCommScan; MPI_Scan, ``exclusive=True``: MPI_Exscan): rank r ends
         with the left fold of ranks 0..r (exclusive: 0..r-1, r > 0) in rank
@@ -170,27 +202,29 @@ class Comm(object):
         from .core import host_scan
         if not _is_tensor(tensor):
             return host_scan(tensor, op, exclusive, comm=self)
+        count, dtype = _elem_args(tensor, op, value)
         _dev._check_tensor(tensor)
         s = stream if stream is not None else _dev.current_stream_ptr(tensor.device)
-        check_call(_LIB.RdcCommScan(self.handle, ctypes.c_void_p(tensor.data_ptr()), tensor.numel(),
-                                    _dev.dtype_enum(tensor.dtype), int(op), 1 if exclusive else 0, s))
+        check_call(_LIB.RdcCommScan(self.handle, ctypes.c_void_p(tensor.data_ptr()), count,
+                                    dtype, int(op), 1 if exclusive else 0, s))
         return tensor
 
-    def allreduce_coalesced(self, tensors, op, algo="auto", stream=None):
+    def allreduce_coalesced(self, tensors, op, algo="auto", stream=None, value=None):
         """Bucketed allreduce of a list of contiguous ROCm tensors of one dtype,
         in place: the result of ``allreduce`` on each tensor in order
         (bit-identical), moved in fused launches.  Returns the list."""
         if not tensors:
             return tensors
+        args = [_elem_args(t, op, value) for t in tensors]
         for t in tensors:
             _dev._check_tensor(t)
             if t.dtype != tensors[0].dtype:
                 raise ValueError("rdc_amd: allreduce_coalesced needs one dtype")
         nb = len(tensors)
         ptrs = (ctypes.c_void_p * nb)(*[t.data_ptr() for t in tensors])
-        counts = (ctypes.c_size_t * nb)(*[t.numel() for t in tensors])
+        counts = (ctypes.c_size_t * nb)(*[a[0] for a in args])
         s = stream if stream is not None else _dev.current_stream_ptr(tensors[0].device)
-        check_call(_LIB.RdcCommAllreduceCoalesced(self.handle, ptrs, counts, nb, _dev.dtype_enum(tensors[0].dtype),
+        check_call(_LIB.RdcCommAllreduceCoalesced(self.handle, ptrs, counts, nb, args[0][1],
                                                   int(op), _ALGOS[algo], s))
         return tensors
 

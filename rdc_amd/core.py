@@ -26,6 +26,11 @@ class Op(Enum):
     MIN = 1
     SUM = 2
     BITOR = 3
+    # MI355X additions (MPI_MAXLOC / MPI_MINLOC) over (value, index) pairs
+    # (F32_I32 / I32_I32): the greatest / least value and, among equal values,
+    # the lowest index
+    MAXLOC = 4
+    MINLOC = 5
 
     def __int__(self):
         return self.value
@@ -33,6 +38,13 @@ class Op(Enum):
 
 # numpy dtype -> mpi::DataType (rdc/core.py:160-169 = include/core/mpi.h:19-30),
 # plus the MI355X additions float16 = 10 (bfloat16 = 11 via torch only)
+# (value, index) pairs of Op.MAXLOC / Op.MINLOC: 8 bytes, the value first.  An
+# array of pairs must be 8-byte aligned (numpy guarantees it for its own
+# allocations); one that is not gets the library's refusal, never a copy.
+# Tensors: torch.int32 [..., 2] with value="float32" | "int32" (Comm.allreduce).
+F32_I32 = np.dtype([("value", np.float32), ("index", np.int32)])
+I32_I32 = np.dtype([("value", np.int32), ("index", np.int32)])
+
 DTYPE_ENUM__ = {
     np.dtype("int8"): 0,
     np.dtype("uint8"): 1,
@@ -43,7 +55,10 @@ DTYPE_ENUM__ = {
     np.dtype("float32"): 6,
     np.dtype("float64"): 7,
     np.dtype("float16"): 10,
+    F32_I32: 12,
+    I32_I32: 13,
 }
+_PAIR_DTYPES = (F32_I32, I32_I32)
 
 
 def init(args=None, lib="standard", lib_dll=None):
@@ -120,20 +135,22 @@ def _torch_dtype_enum(t):
     return device.dtype_enum(t.dtype)
 
 
-def allreduce(data, op, prepare_fun=None):
+def allreduce(data, op, prepare_fun=None, value=None):
     """Allreduce across ranks.
 
     numpy.ndarray: returns the reduced, flattened array (a copy unless ravel
     gave a view of ``data`` — the reference's rule, rdc/core.py:196-217).
     torch.Tensor on a ROCm device: reduced in place on the GPU and returned.
     ``prepare_fun(data)``, if given, runs before the reduction.
+    Op.MAXLOC / Op.MINLOC: a structured array of dtype F32_I32 / I32_I32, or
+    an int32 tensor of pairs read as ``value`` (Comm.allreduce).
     """
     op = int(Op(op) if not isinstance(op, Op) else op)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
         if prepare_fun is not None:
             prepare_fun(data)
-        return _comm.get_comm("main").allreduce(data, op)
+        return _comm.get_comm("main").allreduce(data, op, value=value)
     return host_allreduce(data, op, prepare_fun)
 
 
@@ -144,7 +161,8 @@ def host_allreduce(data, op, prepare_fun=None, comm=None):
     if not isinstance(data, np.ndarray):
         raise TypeError("allreduce only takes in numpy.ndarray or torch.Tensor")
     buf = data.ravel()
-    if buf.base is data.base:
+    misaligned_pairs = buf.dtype in _PAIR_DTYPES and buf.ctypes.data % 8 != 0
+    if buf.base is data.base and not misaligned_pairs:  # those go to the library as they are: it refuses them
         buf = buf.copy()
     if buf.dtype not in DTYPE_ENUM__:
         raise TypeError("data type %s not supported" % str(buf.dtype))
@@ -173,7 +191,7 @@ def split_range(count, n, rank):
     return lo.value, hi.value
 
 
-def reduce_scatter(data, op):
+def reduce_scatter(data, op, value=None):
     """In-place reduce-scatter on the "main" communicator (RdcReduceScatter;
     TryReduceScatterRing, communicator_collective.cc:115-182): chunk
     ``get_rank()`` of ``split_range(data.size, get_world_size(), get_rank())``
@@ -184,7 +202,7 @@ def reduce_scatter(data, op):
     op = int(Op(op) if not isinstance(op, Op) else op)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
-        return _comm.get_comm("main").reduce_scatter(data, op)
+        return _comm.get_comm("main").reduce_scatter(data, op, value=value)
     return host_reduce_scatter(data, op)
 
 
@@ -271,7 +289,7 @@ def host_all_to_all_v(send, send_counts, recv, recv_counts, send_displs=None, re
     return recv
 
 
-def reduce(data, op, root):
+def reduce(data, op, root, value=None):
     """In-place reduction to rank ``root`` on the "main" communicator
     (RdcReduceTo; MPI_Reduce): on ``root`` ``data`` receives the reduction —
     the bits ``allreduce`` puts there by the ring order, at every size — and
@@ -281,7 +299,7 @@ def reduce(data, op, root):
     op = int(Op(op) if not isinstance(op, Op) else op)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
-        return _comm.get_comm("main").reduce(data, op, root)
+        return _comm.get_comm("main").reduce(data, op, root, value=value)
     return host_reduce(data, op, root)
 
 
@@ -301,7 +319,7 @@ def host_reduce(data, op, root, comm=None):
     return data
 
 
-def scan(data, op, exclusive=False):
+def scan(data, op, exclusive=False, value=None):
     """In-place prefix reduction across ranks on the "main" communicator
     (RdcScan; MPI_Scan, ``exclusive=True``: MPI_Exscan): rank r ends with the
     left fold of ranks 0..r (exclusive: 0..r-1, r > 0) in rank order, element
@@ -311,7 +329,7 @@ def scan(data, op, exclusive=False):
     op = int(Op(op) if not isinstance(op, Op) else op)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
-        return _comm.get_comm("main").scan(data, op, exclusive)
+        return _comm.get_comm("main").scan(data, op, exclusive, value=value)
     return host_scan(data, op, exclusive)
 
 
@@ -332,7 +350,7 @@ def host_scan(data, op, exclusive=False, comm=None):
     return data
 
 
-def allreduce_coalesced(arrays, op):
+def allreduce_coalesced(arrays, op, value=None):
     """Bucketed allreduce of a list of arrays of one dtype, in place: the
     result of ``allreduce`` on each one (bit-identical), moved in fused device
     launches (RdcAllreduceCoalesced).  numpy arrays (contiguous) or ROCm
@@ -342,7 +360,7 @@ def allreduce_coalesced(arrays, op):
         return arrays
     if type(arrays[0]).__module__.startswith("torch"):
         from . import comm as _comm
-        return _comm.get_comm("main").allreduce_coalesced(arrays, op)
+        return _comm.get_comm("main").allreduce_coalesced(arrays, op, value=value)
     for a in arrays:
         if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
             raise TypeError("allreduce_coalesced takes contiguous numpy arrays")

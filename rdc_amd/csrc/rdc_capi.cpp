@@ -342,6 +342,18 @@ void check_dtype_op(int dtype, int op) {
     if (op < 0 || op >= RDC_OP_COUNT) throw std::invalid_argument("rdc: bad op " + std::to_string(op));
     if (op == RDC_OP_BITOR && rdc_dtype_is_float(dtype))
         throw std::invalid_argument("rdc: BITOR needs an integer dtype");
+    // MAXLOC / MINLOC fold (value, index) pairs and nothing else folds them
+    if (rdc_op_is_loc(op) != rdc_dtype_is_pair(dtype))
+        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
+                                    std::to_string(op) + "): MAXLOC / MINLOC go with the pair dtypes F32_I32 / "
+                                    "I32_I32 only");
+}
+
+// host buffers of (value, index) pairs: 8-byte aligned like device ones (the
+// staged copies would hide a 4-byte aligned buffer from the device path's check)
+void check_pair_aligned(const void* p, int dtype) {
+    if (rdc_dtype_is_pair(dtype) && (uintptr_t)p % rdc_dtype_size(dtype))
+        throw std::invalid_argument("rdc: buffer not aligned to its element size");
 }
 
 // synchronous allreduce of host or device memory on communicator c
@@ -362,6 +374,7 @@ void allreduce_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, i
         c->WaitNotify(token, s);
         return;
     }
+    check_pair_aligned(sendrecv, dtype);
     // host-resident buffer: pieces of every chunk through pinned slots, H2D /
     // allreduce / D2H overlapped on three streams
     if (!m.host) m.host.reset(new HostPath(c->device(), m.host_zc_bytes));
@@ -384,6 +397,7 @@ void reduce_scatter_sync(Manager& m, Communicator* c, void* sendrecv, size_t cou
     }
     // host buffer: the whole input up, the device reduce-scatter, this rank's
     // chunk back — no other byte of the host buffer is written
+    check_pair_aligned(sendrecv, dtype);
     const size_t esz = rdc_dtype_size(dtype);
     char* d = static_cast<char*>(staging(m, std::max<size_t>(count * esz, 256), c->device()));
     hcheck(hipMemcpyAsync(d, sendrecv, count * esz, hipMemcpyHostToDevice, s), "H2D");
@@ -462,6 +476,7 @@ void allreduce_coalesced_sync(Manager& m, Communicator* c, void** bufs, const si
     }
     if (ndev) throw std::invalid_argument("rdc: coalesced allreduce needs all-host or all-device buffers");
     // host buffers: one HBM image (256-B aligned per buffer), H2D, device path, D2H
+    for (int b = 0; b < nbuf; ++b) check_pair_aligned(bufs[b], dtype);
     const size_t esz = rdc_dtype_size(dtype);
     std::vector<size_t> at((size_t)nbuf);
     size_t total = 0;

@@ -3311,6 +3311,9 @@ void DeviceReduce(void* dst, const void* src, size_t count, int dtype, int op, h
 
 void DeviceFill(void* buf, size_t count, int dtype, uint64_t seed, int rank, hipStream_t stream) {
     if (rdc_dtype_size(dtype) == 0) throw std::invalid_argument("rdc: bad dtype");
+    if (rdc_dtype_is_pair(dtype))
+        throw std::invalid_argument("rdc: RdcFill has no pattern for the pair dtype " + std::to_string(dtype) +
+                                    ": upload (value, index) inputs");
     hip_check(launch_fill(buf, count, dtype, seed, rank, stream), "launch fill");
 }
 

@@ -17,10 +17,27 @@ enum {
     RDC_DT_ULONGLONG = 9,
     RDC_DT_FLOAT16 = 10,
     RDC_DT_BFLOAT16 = 11,
-    RDC_DT_COUNT = 12
+    // (value, index) pairs for RDC_OP_MAXLOC / RDC_OP_MINLOC (MPI_FLOAT_INT /
+    // MPI_2INT): 8 bytes, the value first, then the index.  Buffers of pairs
+    // must be 8-byte aligned (the C struct alone guarantees 4): a 4-byte
+    // aligned one is refused like any buffer not aligned to its element size.
+    RDC_DT_F32_I32 = 12,  // { float value; int32_t index; }
+    RDC_DT_I32_I32 = 13,  // { int32_t value; int32_t index; }
+    RDC_DT_COUNT = 14
 };
 // mpi::OpType (include/core/mpi.h:12-17)
-enum { RDC_OP_MAX = 0, RDC_OP_MIN = 1, RDC_OP_SUM = 2, RDC_OP_BITOR = 3, RDC_OP_COUNT = 4 };
+// + MI355X-build additions MAXLOC / MINLOC (MPI_MAXLOC / MPI_MINLOC), valid
+// with the pair dtypes only, and the pair dtypes with them only:
+//   MaxLoc: dst = src when dst.value < src.value ||
+//                          (dst.value == src.value && src.index < dst.index)
+//   MinLoc: the same with > in the first comparison
+// so, as for Max / Min: a NaN in dst.value stays and a NaN in src.value is
+// ignored; -0.0f == +0.0f is a tie in value (the lower index wins); on a full
+// tie (equal value, equal index) dst stays whole, value bits included, so a
+// +0 / -0 pair with equal indexes depends on the operand order, as NaN does
+// for Max.
+enum { RDC_OP_MAX = 0, RDC_OP_MIN = 1, RDC_OP_SUM = 2, RDC_OP_BITOR = 3, RDC_OP_MAXLOC = 4, RDC_OP_MINLOC = 5,
+       RDC_OP_COUNT = 6 };
 
 // allreduce data-movement schedules
 enum {
@@ -94,10 +111,14 @@ static inline size_t rdc_dtype_size(int dtype) {
         case RDC_DT_INT32: case RDC_DT_UINT32: case RDC_DT_FLOAT32: return 4;
         case RDC_DT_INT64: case RDC_DT_UINT64: case RDC_DT_FLOAT64:
         case RDC_DT_LONGLONG: case RDC_DT_ULONGLONG: return 8;
+        case RDC_DT_F32_I32: case RDC_DT_I32_I32: return 8;
         case RDC_DT_FLOAT16: case RDC_DT_BFLOAT16: return 2;
         default: return 0;
     }
 }
+static inline int rdc_dtype_is_pair(int dtype) { return dtype == RDC_DT_F32_I32 || dtype == RDC_DT_I32_I32; }
+static inline int rdc_op_is_loc(int op) { return op == RDC_OP_MAXLOC || op == RDC_OP_MINLOC; }
+// false for the pair dtypes: no arithmetic is defined on them
 static inline int rdc_dtype_is_float(int dtype) {
     return dtype == RDC_DT_FLOAT32 || dtype == RDC_DT_FLOAT64 || dtype == RDC_DT_FLOAT16 ||
            dtype == RDC_DT_BFLOAT16;

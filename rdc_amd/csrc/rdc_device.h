@@ -6,6 +6,10 @@
 //        Min: dst = (dst > src) ? src : dst
 //        Sum: dst = dst + src                    (signed ints wrap: computed unsigned)
 //        BitOR: dst = dst | src
+//    and the MI355X-build pair operators (rdc_common.h RDC_OP_MAXLOC):
+//        MaxLoc: dst = src if dst.value < src.value ||
+//                           (dst.value == src.value && src.index < dst.index)
+//        MinLoc: the same with >       (NaN, -0 / +0 and full ties: rdc_common.h)
 //    f16: native v_add_f16 (correctly rounded); bf16: f32 add + RNE to bf16.
 //  * 16-byte vector reduce (v4u reinterpreted as 16/sizeof(T) lanes)
 //  * cross-GPU hand-off: write-through (sc0 sc1) payload stores into the
@@ -82,6 +86,43 @@ template <> struct OpF<RDC_OP_BITOR> {
     template <typename T> __device__ __forceinline__ static T apply(T d, T s) {
         typedef typename Arith<T>::U U;
         return (T)((U)d | (U)s);
+    }
+};
+
+// (value, index) pairs (RDC_DT_F32_I32 / RDC_DT_I32_I32): 8 bytes, moved as one
+// 64-bit word by the element-wise paths (ld_elem_sys / st_elem_wt)
+struct alignas(8) pair_f32_t {
+    float value;
+    int32_t index;
+};
+struct alignas(8) pair_i32_t {
+    int32_t value;
+    int32_t index;
+};
+static_assert(sizeof(pair_f32_t) == 8 && std::is_trivially_copyable<pair_f32_t>::value, "pair_f32_t");
+static_assert(sizeof(pair_i32_t) == 8 && std::is_trivially_copyable<pair_i32_t>::value, "pair_i32_t");
+
+// does src replace dst?  Non-short-circuit on purpose: two compares, one
+// and, one or, no branch.
+template <bool MAX, typename V>
+__device__ __forceinline__ bool loc_take(V dv, int32_t di, V sv, int32_t si) {
+    const bool better = MAX ? (dv < sv) : (dv > sv);
+    return better | ((dv == sv) & (si < di));
+}
+template <> struct OpF<RDC_OP_MAXLOC> {
+    __device__ __forceinline__ static pair_f32_t apply(pair_f32_t d, pair_f32_t s) {
+        return loc_take<true>(d.value, d.index, s.value, s.index) ? s : d;
+    }
+    __device__ __forceinline__ static pair_i32_t apply(pair_i32_t d, pair_i32_t s) {
+        return loc_take<true>(d.value, d.index, s.value, s.index) ? s : d;
+    }
+};
+template <> struct OpF<RDC_OP_MINLOC> {
+    __device__ __forceinline__ static pair_f32_t apply(pair_f32_t d, pair_f32_t s) {
+        return loc_take<false>(d.value, d.index, s.value, s.index) ? s : d;
+    }
+    __device__ __forceinline__ static pair_i32_t apply(pair_i32_t d, pair_i32_t s) {
+        return loc_take<false>(d.value, d.index, s.value, s.index) ? s : d;
     }
 };
 
@@ -163,6 +204,33 @@ __device__ __forceinline__ v4u reduce16<RDC_OP_SUM, bf16_t>(v4u d, v4u s) {
     }
     return out;
 }
+
+// (value, index) pairs, two per vector, folded from the four dwords: per pair
+// two compares on the value dwords, one on the index dwords, and both dwords
+// selected under the one condition (v_cmp x3, two mask ops, v_cndmask x2)
+namespace loc16 {
+template <bool MAX, bool FLOAT>
+__device__ __forceinline__ v4u reduce(v4u d, v4u s) {
+    v4u out;
+#pragma unroll
+    for (int k = 0; k < 4; k += 2) {
+        const int32_t di = (int32_t)d[k + 1], si = (int32_t)s[k + 1];
+        const bool take = FLOAT ? loc_take<MAX>(__uint_as_float(d[k]), di, __uint_as_float(s[k]), si)
+                                : loc_take<MAX>((int32_t)d[k], di, (int32_t)s[k], si);
+        out[k] = take ? s[k] : d[k];
+        out[k + 1] = take ? s[k + 1] : d[k + 1];
+    }
+    return out;
+}
+}  // namespace loc16
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_MAXLOC, pair_f32_t>(v4u d, v4u s) { return loc16::reduce<true, true>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_MINLOC, pair_f32_t>(v4u d, v4u s) { return loc16::reduce<false, true>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_MAXLOC, pair_i32_t>(v4u d, v4u s) { return loc16::reduce<true, false>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_MINLOC, pair_i32_t>(v4u d, v4u s) { return loc16::reduce<false, false>(d, s); }
 
 // ------------------------------------------------------- memory access ----
 __device__ __forceinline__ v4u ld16(const void* p) { return *reinterpret_cast<const v4u*>(p); }

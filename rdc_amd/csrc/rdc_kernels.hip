@@ -1,6 +1,6 @@
 // MI355X (gfx950) kernels of the rdc path that do not depend on the reduction
 // operator (broadcast, synthetic fill) and the (dtype, op) dispatch.
-//   per-operator instantiations: rdc_kernels_{max,min,sum,bitor}.hip
+//   per-operator instantiations: rdc_kernels_{max,min,sum,bitor,loc}.hip
 //   device templates:            rdc_kernels_impl.h
 #include "rdc_kernels_impl.h"
 
@@ -241,6 +241,8 @@ bool pick_max(int dtype, KernelSet* ks);
 bool pick_min(int dtype, KernelSet* ks);
 bool pick_sum(int dtype, KernelSet* ks);
 bool pick_bitor(int dtype, KernelSet* ks);
+bool pick_maxloc(int dtype, KernelSet* ks);
+bool pick_minloc(int dtype, KernelSet* ks);
 
 bool get_kernels(int dtype, int op, KernelSet* ks) {
     switch (op) {
@@ -248,6 +250,8 @@ bool get_kernels(int dtype, int op, KernelSet* ks) {
         case RDC_OP_MIN: return pick_min(dtype, ks);
         case RDC_OP_SUM: return pick_sum(dtype, ks);
         case RDC_OP_BITOR: return pick_bitor(dtype, ks);
+        case RDC_OP_MAXLOC: return pick_maxloc(dtype, ks);
+        case RDC_OP_MINLOC: return pick_minloc(dtype, ks);
         default: return false;
     }
 }

@@ -1736,8 +1736,22 @@ __device__ __forceinline__ bool ll_match(const v4u& lo, const v4u& hi, uint32_t 
 // every instruction 64 separate 16-byte requests).
 // HX: compiled with the host exchange (a.hx set); the default variant keeps
 // its polling arrays out of the register budget
+// Waves per SIMD the service block is compiled for: BS / 256, which is what its
+// launch bounds imply anyway — except the (value, index) pair types' 16-rank
+// host-exchange variant, compiled for 2 so that it stays below 256 VGPRs like
+// every other kernel of theirs (the compiler otherwise spreads that one
+// resident 256-thread block over 306 registers).  Its 128 KiB of LDS still
+// allow one block per CU only, which hipcc reports for those four
+// instantiations ("failed to meet occupancy target"): the register budget is
+// what the attribute is for.
+template <typename T, int NMAX, int BS, bool HX>
+struct SvcWaves {
+    static constexpr bool kPair = std::is_same<T, pair_f32_t>::value || std::is_same<T, pair_i32_t>::value;
+    static constexpr int kMin = (kPair && NMAX == 16 && BS == 256 && HX) ? 2 : BS / 256;
+};
 template <int OP, typename T, int NMAX, int BS, bool HX>
-__global__ __launch_bounds__(BS) void k_svc(SvcArgs a) {
+__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(SvcWaves<T, NMAX, BS, HX>::kMin)))
+void k_svc(SvcArgs a) {
     constexpr int L = 16 / sizeof(T);  // elements per vector
     constexpr int U = 4;               // input vectors in flight per thread
     typedef typename std::conditional<sizeof(T) == 1, uint8_t,
@@ -2222,6 +2236,16 @@ inline bool pick_arith(int dtype, KernelSet* ks) {
         case RDC_DT_FLOAT64: RDC_SET(double)
         case RDC_DT_FLOAT16: RDC_SET(_Float16)
         case RDC_DT_BFLOAT16: RDC_SET(bf16_t)
+        default: return false;
+    }
+}
+
+// (value, index) pairs (MaxLoc, MinLoc): the pair dtypes and nothing else
+template <int OP>
+inline bool pick_loc(int dtype, KernelSet* ks) {
+    switch (dtype) {
+        case RDC_DT_F32_I32: RDC_SET(pair_f32_t)
+        case RDC_DT_I32_I32: RDC_SET(pair_i32_t)
         default: return false;
     }
 }

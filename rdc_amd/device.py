@@ -55,3 +55,28 @@ def fill_(t, seed, rank, stream=None):
     s = stream if stream is not None else current_stream_ptr(t.device)
     check_call(_LIB.RdcFill(ctypes.c_void_p(t.data_ptr()), t.numel(), dtype_enum(t.dtype), seed, rank, s))
     return t
+
+
+def pack_pairs(values, indices):
+    """(value, index) pairs for Op.MAXLOC / Op.MINLOC as torch has no struct
+    dtype: a contiguous ``torch.int32`` tensor of shape ``values.shape + (2,)``
+    holding each value's bits (``values``: float32 or int32) and its index.
+    Plain torch code, a convenience beside the hot path."""
+    import torch
+    if values.dtype not in (torch.float32, torch.int32):
+        raise TypeError("rdc_amd: pack_pairs takes float32 or int32 values, got %s" % values.dtype)
+    if indices.shape != values.shape:
+        raise ValueError("rdc_amd: pack_pairs needs values and indices of one shape")
+    return torch.stack((values.contiguous().view(torch.int32), indices.to(torch.int32)), dim=-1).contiguous()
+
+
+def unpack_pairs(pairs, value="float32"):
+    """``(values, indices)`` of a tensor made by ``pack_pairs``; ``value`` says
+    how to read the value bits ("float32" or "int32")."""
+    import torch
+    if pairs.dtype != torch.int32 or pairs.dim() < 1 or pairs.shape[-1] != 2:
+        raise TypeError("rdc_amd: unpack_pairs takes a torch.int32 tensor whose last dimension is 2")
+    if value not in ("float32", "int32"):
+        raise TypeError("rdc_amd: value must be \"float32\" or \"int32\", got %r" % (value,))
+    v = pairs[..., 0].contiguous()
+    return (v.view(torch.float32) if value == "float32" else v), pairs[..., 1].contiguous()

@@ -44,6 +44,11 @@ construction.  Per form the median over rounds of the slowest rank's time per
 call and the spread.  Next to them scan_hbm_fraction = the scan's modelled HBM
 bytes (RdcPlanScanBytes, read + write, summed over the ranks: they share one
 GPU) per pipelined call over the HBM peak.
+SWEEP_DTYPE / SWEEP_OP pick the element type and operator of the allreduce,
+reduce_to and scan modes: f32 (default) / i64 / f32_i32 and sum (default) / max
+/ maxloc.  SWEEP_DTYPE=f32_i32 SWEEP_OP=maxloc times MaxLoc over (value, index)
+pairs, its inputs uploaded from numpy (RdcFill has no pattern for pairs);
+SWEEP_DTYPE=i64 SWEEP_OP=max is its yardstick at the same byte sizes.
 
     python -m torch.distributed.run --nproc-per-node N tools/algo_sweep.py [sizes_MiB] [steps]
 """
@@ -58,6 +63,29 @@ sys.path.insert(0, ROOT)
 
 
 HBM_PEAK = 8.0e12  # bytes / s, one MI355X
+
+# element type and operator of the allreduce / reduce_to / scan modes
+DT, ESZ = {"f32": (6, 4), "i64": (4, 8), "f32_i32": (12, 8)}[os.environ.get("SWEEP_DTYPE", "f32")]
+OP = {"sum": 2, "max": 0, "maxloc": 4}[os.environ.get("SWEEP_OP", "sum")]
+
+
+def fill_input(buf, rank):
+    """Synthetic input over the whole buffer: RdcFill, or for pairs an upload
+    from numpy (values from a small set so that ranks tie, index = rank)."""
+    import rdc_amd
+    if DT != 12:
+        from rdc_amd._lib import _LIB, check_call
+        import torch
+        check_call(_LIB.RdcFill(ctypes.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size() // ESZ, DT,
+                                0x5EED0000, rank, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(0x5EED0000 + rank)
+    x = np.empty(buf.numel() * buf.element_size() // 8, dtype=rdc_amd.F32_I32)
+    x["value"] = rng.integers(-4, 5, x.size).astype(np.float32)
+    x["index"] = rank
+    buf.view(torch.uint8).copy_(torch.from_numpy(x.view(np.uint8)))
 
 
 def alltoall_sweep(sizes, steps, rank, world, comm, sp):
@@ -150,20 +178,20 @@ def reduce_to_sweep(sizes, steps, rank, world, comm, sp):
     rounds = int(os.environ.get("SWEEP_ROUNDS", "5"))
     big = int(max(sizes) * (1 << 20))
     buf = torch.empty(big // 4, dtype=torch.float32, device="cuda")
-    rdc_amd.fill_(buf, 0x5EED0000, rank)
+    fill_input(buf, rank)
     p = ctypes.c_void_p(buf.data_ptr())
     out = {}
     for mib in sizes:
         nb = int(mib * (1 << 20))
 
         def rooted():
-            check_call(_LIB.RdcCommReduceTo(comm.handle, p, nb // 4, 6, 2, 0, sp))
+            check_call(_LIB.RdcCommReduceTo(comm.handle, p, nb // ESZ, DT, OP, 0, sp))
 
         def mesh():
-            check_call(_LIB.RdcCommAllreduceEx(comm.handle, p, nb // 4, 6, 2, 2, sp))
+            check_call(_LIB.RdcCommAllreduceEx(comm.handle, p, nb // ESZ, DT, OP, 2, sp))
 
         def auto():
-            check_call(_LIB.RdcCommAllreduceEx(comm.handle, p, nb // 4, 6, 2, 0, sp))
+            check_call(_LIB.RdcCommAllreduceEx(comm.handle, p, nb // ESZ, DT, OP, 0, sp))
 
         def timed(fn, n_steps, sync):
             torch.cuda.synchronize()
@@ -206,8 +234,8 @@ def reduce_to_sweep(sizes, steps, rank, world, comm, sp):
         comm.check(sp)
         row["root_grid_scatter_reduce_gather_tile"] = [int(x) for x in ll[:5]]
         m, full = (ctypes.c_uint64 * 5)(), (ctypes.c_uint64 * 5)()
-        check_call(_LIB.RdcPlanReduceToBytes(world, -1, 0, nb // 4, 6, m))
-        check_call(_LIB.RdcPlanHbmBytes(world, nb // 4, 6, 2, full))
+        check_call(_LIB.RdcPlanReduceToBytes(world, -1, 0, nb // ESZ, DT, m))
+        check_call(_LIB.RdcPlanHbmBytes(world, nb // ESZ, DT, 2, full))
         row["reduce_to_bytes_ratio"] = round((m[2] + m[3]) / float(full[2] + full[3]), 4)
         row["reduce_to_hbm_fraction"] = round((m[2] + m[3]) / (row["reduce_to"] * 1e-3) / HBM_PEAK, 4)
         row["speedup_vs_mesh"] = round(row["allreduce_mesh"] / row["reduce_to"], 3)
@@ -235,18 +263,18 @@ def scan_sweep(sizes, steps, rank, world, comm, sp):
     out = {}
     for mib in sizes:
         nb = int(mib * (1 << 20))
-        rdc_amd.fill_(buf, 0x5EED0000, rank)   # sums of sums overflow after enough calls: fresh values per size
+        fill_input(buf, rank)   # sums of sums overflow after enough calls: fresh values per size
 
         def scan():
-            check_call(_LIB.RdcCommScan(comm.handle, p, nb // 4, 6, 2, 0, sp))
+            check_call(_LIB.RdcCommScan(comm.handle, p, nb // ESZ, DT, OP, 0, sp))
 
         def ring():
-            check_call(_LIB.RdcCommAllreduceEx(comm.handle, p, nb // 4, 6, 2, 1, sp))
+            check_call(_LIB.RdcCommAllreduceEx(comm.handle, p, nb // ESZ, DT, OP, 1, sp))
 
         def composed():  # the same prefix as a user of the parent commit writes it
             if rank > 0:
                 comm.recv(tmp[: nb // 4], rank - 1)
-                check_call(_LIB.RdcReduce(p, q, nb // 4, 6, 2, sp))
+                check_call(_LIB.RdcReduce(p, q, nb // ESZ, DT, OP, sp))
             if rank < world - 1:
                 comm.send(buf[: nb // 4], rank + 1)
 
@@ -289,7 +317,7 @@ def scan_sweep(sizes, steps, rank, world, comm, sp):
         comm.check(sp)
         row["scan_grid_tile"] = [int(ll[0]), int(ll[4])]
         m = (ctypes.c_uint64 * 5)()
-        check_call(_LIB.RdcPlanScanBytes(world, -1, nb // 4, 6, m))
+        check_call(_LIB.RdcPlanScanBytes(world, -1, nb // ESZ, DT, m))
         row["scan_hbm_fraction"] = round((m[2] + m[3]) / (row["scan"] * 1e-3) / HBM_PEAK, 4)
         row["speedup_vs_composed"] = round(row["composed"] / row["scan_sync"], 2)   # both complete every call
         row["scan_over_ring"] = round(row["scan"] / row["allreduce_ring"], 3)
@@ -332,7 +360,7 @@ def main():
     check_call(_LIB.RdcCommGetParam(comm.handle, b"slot_bytes", ctypes.byref(half)))
     big = int(max(sizes) * (1 << 20))
     buf = torch.empty(big // 4, dtype=torch.float32, device="cuda")
-    rdc_amd.fill_(buf, 0x5EED0000, rank)
+    fill_input(buf, rank)
     rs_mode = os.environ.get("SWEEP_COLLECTIVE", "allreduce") == "reduce_scatter"
     out = {}
     for mib in sizes:
@@ -351,10 +379,10 @@ def main():
 
             def one():
                 if scatter:
-                    check_call(_LIB.RdcCommReduceScatter(comm.handle, ctypes.c_void_p(buf.data_ptr()), nb // 4, 6, 2,
+                    check_call(_LIB.RdcCommReduceScatter(comm.handle, ctypes.c_void_p(buf.data_ptr()), nb // ESZ, DT, OP,
                                                          algo, sp))
                 else:
-                    check_call(_LIB.RdcCommAllreduceEx(comm.handle, ctypes.c_void_p(buf.data_ptr()), nb // 4, 6, 2,
+                    check_call(_LIB.RdcCommAllreduceEx(comm.handle, ctypes.c_void_p(buf.data_ptr()), nb // ESZ, DT, OP,
                                                        algo, sp))
 
             def stats():
@@ -394,8 +422,8 @@ def main():
                 row[name + "_export_us"] = round(float(v[1]), 2)
         if rs_mode:
             m, full = (ctypes.c_uint64 * 5)(), (ctypes.c_uint64 * 5)()
-            check_call(_LIB.RdcPlanReduceScatterBytes(world, nb // 4, 6, 6, m))
-            check_call(_LIB.RdcPlanHbmBytes(world, nb // 4, 6, 6, full))
+            check_call(_LIB.RdcPlanReduceScatterBytes(world, nb // ESZ, DT, 6, m))
+            check_call(_LIB.RdcPlanHbmBytes(world, nb // ESZ, DT, 6, full))
             row["rs_direct_hbm_fraction"] = round((m[0] + m[1]) / float(full[0] + full[1]), 4)
         out["%g MiB" % mib] = row
     if rank == 0:
