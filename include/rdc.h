@@ -69,7 +69,11 @@ enum OpType {
     kBitwiseOR = 3,
     /*! \brief MI355X additions (MPI_MAXLOC / MPI_MINLOC) over ValueIndex<V> */
     kMaxLoc = 4,
-    kMinLoc = 5
+    kMinLoc = 5,
+    /*! \brief MI355X additions (MPI_PROD / MPI_BAND / MPI_BXOR); 6 and 7 are unassigned */
+    kProd = 8,
+    kBitwiseAND = 9,
+    kBitwiseXOR = 10
 };
 /*! \brief element types (include/core/mpi.h:19-30) */
 enum DataType {
@@ -149,6 +153,41 @@ struct BitOR {
     static const mpi::OpType kType = mpi::kBitwiseOR;
     template <typename DType> inline static void Reduce(DType& dst, const DType& src) {  // NOLINT(*)
         dst |= src;
+    }
+};
+/*! \brief MI355X addition (MPI_PROD): dst = dst * src.  Integers wrap modulo
+ *  2^bits: the product is taken on the unsigned type (a signed `dst *= src`
+ *  is undefined on overflow), which gives the device kernel's bits.  float and
+ *  double: one IEEE multiply, round-to-nearest-even, subnormals kept (build
+ *  host code without fast-math or flush-to-zero for equal bits). */
+struct Prod {
+    static const mpi::OpType kType = mpi::kProd;
+    template <typename DType>
+    inline static typename std::enable_if<std::is_integral<DType>::value>::type
+    Reduce(DType& dst, const DType& src) {  // NOLINT(*)
+        typedef typename std::make_unsigned<DType>::type U;
+        // unsigned int at the least: narrower types would promote to (signed) int
+        typedef typename std::conditional<(sizeof(U) < sizeof(unsigned)), unsigned, U>::type W;
+        dst = static_cast<DType>(static_cast<U>(static_cast<W>(static_cast<U>(dst)) * static_cast<W>(static_cast<U>(src))));
+    }
+    template <typename DType>
+    inline static typename std::enable_if<std::is_floating_point<DType>::value>::type
+    Reduce(DType& dst, const DType& src) {  // NOLINT(*)
+        dst *= src;
+    }
+};
+/*! \brief MI355X additions (MPI_BAND / MPI_BXOR): integer types only, as
+ *  BitOR (they do not compile for float or double) */
+struct BitAND {
+    static const mpi::OpType kType = mpi::kBitwiseAND;
+    template <typename DType> inline static void Reduce(DType& dst, const DType& src) {  // NOLINT(*)
+        dst &= src;
+    }
+};
+struct BitXOR {
+    static const mpi::OpType kType = mpi::kBitwiseXOR;
+    template <typename DType> inline static void Reduce(DType& dst, const DType& src) {  // NOLINT(*)
+        dst ^= src;
     }
 };
 /*! \brief MI355X additions (MPI_MAXLOC / MPI_MINLOC) over ValueIndex<V>:

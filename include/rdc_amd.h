@@ -38,6 +38,23 @@
  *     13 only, and those dtypes with MAXLOC / MINLOC only: every other
  *     combination is refused before anything is launched, the message naming
  *     both.  RdcFill refuses the pair dtypes (upload the inputs).
+ *     MI355X additions (MPI_PROD / MPI_BAND / MPI_BXOR), dst = OP(dst, src):
+ *       8 PROD   dst * src   every arithmetic dtype 0-11
+ *       9 BITAND dst & src   integer dtypes only, as BITOR
+ *      10 BITXOR dst ^ src   integer dtypes only
+ *     Codes 6 and 7 are unassigned and refused as "bad op 6" / "bad op 7"
+ *     (both have long served callers as the example of an unknown operator);
+ *     11 and above likewise.
+ *     PROD on integers wraps modulo 2^bits (computed on the unsigned type, as
+ *     SUM).  On float32, float64 and float16 it is one IEEE multiply,
+ *     round-to-nearest-even, subnormals kept.  On bfloat16 it is the float32
+ *     product of the two widened values (exact), rounded to bfloat16 once
+ *     (RNE): the correctly rounded product.  NaN payloads are not pinned.  The
+ *     fold orders are SUM's (ring order per chunk, tree order at or below
+ *     rdc_reduce_ring_mincount, rank order for scans), and they decide a
+ *     floating product's bits exactly as they decide a sum's.  BITAND / BITXOR
+ *     with a float dtype and any of the three with a pair dtype are refused
+ *     before anything is launched.
  *   - results are bit-identical to the reference's CPU ring allreduce
  *     (src/comm/communicator_collective.cc:115-203) on the same inputs.
  */

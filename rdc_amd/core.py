@@ -31,6 +31,12 @@ class Op(Enum):
     # the lowest index
     MAXLOC = 4
     MINLOC = 5
+    # MI355X additions (MPI_PROD / MPI_BAND / MPI_BXOR); 6 and 7 are unassigned.
+    # PROD: every arithmetic dtype (integers wrap; bf16: exact f32 product
+    # rounded once); BITAND / BITXOR: integer dtypes only, as BITOR
+    PROD = 8
+    BITAND = 9
+    BITXOR = 10
 
     def __int__(self):
         return self.value

@@ -339,9 +339,15 @@ namespace {
 
 void check_dtype_op(int dtype, int op) {
     if (rdc_dtype_size(dtype) == 0) throw std::invalid_argument("rdc: bad dtype " + std::to_string(dtype));
-    if (op < 0 || op >= RDC_OP_COUNT) throw std::invalid_argument("rdc: bad op " + std::to_string(op));
+    // codes 6 and 7 are unassigned (8-10 are PROD / BITAND / BITXOR)
+    if (op < 0 || op >= RDC_OP_COUNT || op == RDC_OP_UNASSIGNED_6 || op == RDC_OP_UNASSIGNED_7)
+        throw std::invalid_argument("rdc: bad op " + std::to_string(op));
     if (op == RDC_OP_BITOR && rdc_dtype_is_float(dtype))
         throw std::invalid_argument("rdc: BITOR needs an integer dtype");
+    if (op == RDC_OP_BITAND && rdc_dtype_is_float(dtype))
+        throw std::invalid_argument("rdc: BITAND needs an integer dtype");
+    if (op == RDC_OP_BITXOR && rdc_dtype_is_float(dtype))
+        throw std::invalid_argument("rdc: BITXOR needs an integer dtype");
     // MAXLOC / MINLOC fold (value, index) pairs and nothing else folds them
     if (rdc_op_is_loc(op) != rdc_dtype_is_pair(dtype))
         throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +

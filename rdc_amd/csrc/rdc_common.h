@@ -36,8 +36,21 @@ enum {
 // tie (equal value, equal index) dst stays whole, value bits included, so a
 // +0 / -0 pair with equal indexes depends on the operand order, as NaN does
 // for Max.
+// + PROD / BITAND / BITXOR (MPI_PROD / MPI_BAND / MPI_BXOR), dst = OP(dst, src):
+//   Prod:   dst * src.  Integers wrap modulo 2^bits (computed on the unsigned
+//           type, as Sum is).  float32 / float64 / float16: one IEEE multiply,
+//           round-to-nearest-even, subnormals kept (the build has
+//           -ffp-contract=off -fno-fast-math and no flush flag).  bfloat16: the
+//           f32 product of the two widened values, which is exact, rounded to
+//           bf16 once (RNE): the correctly rounded bf16 product; NaN as
+//           f32_to_bf16 does.  NaN payloads are not pinned.  The fold orders
+//           are Sum's (a floating product is not associative either).
+//   BitAND: dst & src, BitXOR: dst ^ src; integer dtypes only, as BitOR.
+//   None of the three takes a pair dtype.  Codes 6 and 7 are unassigned and
+//   refused (callers have long used both as their example of an unknown op).
 enum { RDC_OP_MAX = 0, RDC_OP_MIN = 1, RDC_OP_SUM = 2, RDC_OP_BITOR = 3, RDC_OP_MAXLOC = 4, RDC_OP_MINLOC = 5,
-       RDC_OP_COUNT = 6 };
+       RDC_OP_UNASSIGNED_6 = 6, RDC_OP_UNASSIGNED_7 = 7, RDC_OP_PROD = 8, RDC_OP_BITAND = 9, RDC_OP_BITXOR = 10,
+       RDC_OP_COUNT = 11 };
 
 // allreduce data-movement schedules
 enum {

@@ -6,6 +6,11 @@
 //        Min: dst = (dst > src) ? src : dst
 //        Sum: dst = dst + src                    (signed ints wrap: computed unsigned)
 //        BitOR: dst = dst | src
+//    the MI355X-build additions (rdc_common.h RDC_OP_PROD):
+//        Prod: dst = dst * src     (ints wrap modulo 2^bits: computed unsigned;
+//              f32 / f64 / f16: one IEEE multiply, RNE, subnormals kept;
+//              bf16: exact f32 product + one RNE to bf16)
+//        BitAND: dst = dst & src,  BitXOR: dst = dst ^ src   (integers only)
 //    and the MI355X-build pair operators (rdc_common.h RDC_OP_MAXLOC):
 //        MaxLoc: dst = src if dst.value < src.value ||
 //                           (dst.value == src.value && src.index < dst.index)
@@ -89,6 +94,38 @@ template <> struct OpF<RDC_OP_BITOR> {
     }
 };
 
+template <> struct OpF<RDC_OP_PROD> {
+    // integers on the unsigned type: the product wraps modulo 2^bits (a signed
+    // `d * s` is undefined on overflow); bytes promote to int, 255 * 255 fits
+    template <typename T> __device__ __forceinline__ static T apply(T d, T s) {
+        typedef typename Arith<T>::U U;
+        return (T)((U)d * (U)s);
+    }
+    __device__ __forceinline__ static float apply(float d, float s) { return d * s; }
+    __device__ __forceinline__ static double apply(double d, double s) { return d * s; }
+    __device__ __forceinline__ static _Float16 apply(_Float16 d, _Float16 s) { return d * s; }
+    // the f32 product of two bf16 values is exact (8 x 8 significand bits), so
+    // one RNE conversion gives the correctly rounded bf16 product
+    __device__ __forceinline__ static bf16_t apply(bf16_t d, bf16_t s) {
+        const __bf16 h = (__bf16)(bf16_to_f32(d.bits) * bf16_to_f32(s.bits));
+        bf16_t r;
+        r.bits = __builtin_bit_cast(uint16_t, h);
+        return r;
+    }
+};
+template <> struct OpF<RDC_OP_BITAND> {
+    template <typename T> __device__ __forceinline__ static T apply(T d, T s) {
+        typedef typename Arith<T>::U U;
+        return (T)((U)d & (U)s);
+    }
+};
+template <> struct OpF<RDC_OP_BITXOR> {
+    template <typename T> __device__ __forceinline__ static T apply(T d, T s) {
+        typedef typename Arith<T>::U U;
+        return (T)((U)d ^ (U)s);
+    }
+};
+
 // (value, index) pairs (RDC_DT_F32_I32 / RDC_DT_I32_I32): 8 bytes, moved as one
 // 64-bit word by the element-wise paths (ld_elem_sys / st_elem_wt)
 struct alignas(8) pair_f32_t {
@@ -145,7 +182,12 @@ __device__ __forceinline__ v4u reduce16(v4u d, v4u s) {
 // reference's `dst += src` on a byte: low 7 bits added without carry-out,
 // top bit by XOR.  Max / Min: even and odd bytes as 16-bit lanes through
 // v_pk_max_u16 / v_pk_min_u16; signed bytes compare as unsigned after
-// flipping their sign bits.
+// flipping their sign bits.  Prod wraps modulo 256 and the signed product has
+// the same bits: the low byte of a 16-bit lane's product depends on the
+// operands' low bytes only, so the even bytes are the masked v_pk_mul_lo_u16 of
+// the dwords as they are, and the odd bytes come out in place, low byte zero,
+// from (a & 0xff00ff00) * (b >> 8): (x << 8) * y mod 2^16 = ((x * y) & 0xff) << 8
+// whatever sits above y's low byte.  BitAND / BitXOR: one VALU op per dword.
 namespace swar8 {
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t add(uint32_t a, uint32_t b) {
@@ -159,6 +201,11 @@ __device__ __forceinline__ uint32_t pick_u(uint32_t a, uint32_t b) {
     const u16x2 o = MAX ? __builtin_elementwise_max(ao, bo) : __builtin_elementwise_min(ao, bo);
     return __builtin_bit_cast(uint32_t, e) | (__builtin_bit_cast(uint32_t, o) << 8);
 }
+__device__ __forceinline__ uint32_t mul(uint32_t a, uint32_t b) {
+    const u16x2 e = __builtin_bit_cast(u16x2, a) * __builtin_bit_cast(u16x2, b);
+    const u16x2 o = __builtin_bit_cast(u16x2, a & 0xff00ff00u) * __builtin_bit_cast(u16x2, b >> 8);
+    return (__builtin_bit_cast(uint32_t, e) & 0x00ff00ffu) | __builtin_bit_cast(uint32_t, o);
+}
 template <int OP, bool SIGNED>
 __device__ __forceinline__ v4u reduce(v4u d, v4u s) {
     constexpr uint32_t flip = SIGNED ? 0x80808080u : 0u;
@@ -167,6 +214,9 @@ __device__ __forceinline__ v4u reduce(v4u d, v4u s) {
     for (int k = 0; k < 4; ++k) {
         if (OP == RDC_OP_SUM) out[k] = add(d[k], s[k]);
         else if (OP == RDC_OP_BITOR) out[k] = d[k] | s[k];
+        else if (OP == RDC_OP_BITAND) out[k] = d[k] & s[k];
+        else if (OP == RDC_OP_BITXOR) out[k] = d[k] ^ s[k];
+        else if (OP == RDC_OP_PROD) out[k] = mul(d[k], s[k]);
         else out[k] = pick_u<OP == RDC_OP_MAX>(d[k] ^ flip, s[k] ^ flip) ^ flip;
     }
     return out;
@@ -188,6 +238,18 @@ template <>
 __device__ __forceinline__ v4u reduce16<RDC_OP_MIN, uint8_t>(v4u d, v4u s) { return swar8::reduce<RDC_OP_MIN, false>(d, s); }
 template <>
 __device__ __forceinline__ v4u reduce16<RDC_OP_MIN, int8_t>(v4u d, v4u s) { return swar8::reduce<RDC_OP_MIN, true>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_PROD, uint8_t>(v4u d, v4u s) { return swar8::reduce<RDC_OP_PROD, false>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_PROD, int8_t>(v4u d, v4u s) { return swar8::reduce<RDC_OP_PROD, true>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_BITAND, uint8_t>(v4u d, v4u s) { return swar8::reduce<RDC_OP_BITAND, false>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_BITAND, int8_t>(v4u d, v4u s) { return swar8::reduce<RDC_OP_BITAND, true>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_BITXOR, uint8_t>(v4u d, v4u s) { return swar8::reduce<RDC_OP_BITXOR, false>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_BITXOR, int8_t>(v4u d, v4u s) { return swar8::reduce<RDC_OP_BITXOR, true>(d, s); }
 
 // bf16 Sum, two lanes per dword: v_pk_add_f32 + v_cvt_pk_bf16_f32 instead of
 // a software round per element (the generic loop runs 4.35 TB/s, ALU-bound)
@@ -204,6 +266,10 @@ __device__ __forceinline__ v4u reduce16<RDC_OP_SUM, bf16_t>(v4u d, v4u s) {
     }
     return out;
 }
+// bf16 Prod has no such form: OpF<RDC_OP_PROD>::apply converts through __bf16,
+// so the generic loop already rounds in hardware (v_cvt_pk_bf16_f32), and a
+// v_pk_mul_f32 form shaped like the one above measured no faster in k_reduce on
+// 1 GiB (0.5147 against 0.5144 ms)
 
 // (value, index) pairs, two per vector, folded from the four dwords: per pair
 // two compares on the value dwords, one on the index dwords, and both dwords

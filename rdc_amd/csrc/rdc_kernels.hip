@@ -1,6 +1,6 @@
 // MI355X (gfx950) kernels of the rdc path that do not depend on the reduction
 // operator (broadcast, synthetic fill) and the (dtype, op) dispatch.
-//   per-operator instantiations: rdc_kernels_{max,min,sum,bitor,loc}.hip
+//   per-operator instantiations: rdc_kernels_{max,min,sum,bitor,loc,prod,bitand,bitxor}.hip
 //   device templates:            rdc_kernels_impl.h
 #include "rdc_kernels_impl.h"
 
@@ -243,6 +243,9 @@ bool pick_sum(int dtype, KernelSet* ks);
 bool pick_bitor(int dtype, KernelSet* ks);
 bool pick_maxloc(int dtype, KernelSet* ks);
 bool pick_minloc(int dtype, KernelSet* ks);
+bool pick_prod(int dtype, KernelSet* ks);
+bool pick_bitand(int dtype, KernelSet* ks);
+bool pick_bitxor(int dtype, KernelSet* ks);
 
 bool get_kernels(int dtype, int op, KernelSet* ks) {
     switch (op) {
@@ -252,6 +255,9 @@ bool get_kernels(int dtype, int op, KernelSet* ks) {
         case RDC_OP_BITOR: return pick_bitor(dtype, ks);
         case RDC_OP_MAXLOC: return pick_maxloc(dtype, ks);
         case RDC_OP_MINLOC: return pick_minloc(dtype, ks);
+        case RDC_OP_PROD: return pick_prod(dtype, ks);
+        case RDC_OP_BITAND: return pick_bitand(dtype, ks);
+        case RDC_OP_BITXOR: return pick_bitxor(dtype, ks);
         default: return false;
     }
 }

@@ -2227,7 +2227,7 @@ inline bool pick_int(int dtype, KernelSet* ks) {
     }
 }
 
-// integer and floating element types (Max, Min, Sum)
+// integer and floating element types (Max, Min, Sum, Prod)
 template <int OP>
 inline bool pick_arith(int dtype, KernelSet* ks) {
     if (pick_int<OP>(dtype, ks)) return true;
