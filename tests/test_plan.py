@@ -5,7 +5,9 @@ Checks that for every (n, count, dtype, scratch) the launches cover each
 Split chunk (include/utils/utils.h:59-70) exactly once, in order, that every
 piece fits its scratch slot, tiles and flag indices stay in range, and the
 scratch placement is rank-independent (off % 16)."""
+import collections
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -182,6 +184,165 @@ def test_mixed_plan_is_deterministic():
     assert {op["kind"] for op in a} >= {"allreduce", "bcast", "allgather", "coalesced"}
     small = make_plan(5, 6, 2)
     assert expected(small, 2).size == output_bytes(small)
+
+
+# (seed, world) of tests/test_gpu_mixed.py::test_cover_chain_every_adjacent_pair
+COVER_CASES = [(21, 3), (22, 4), (23, 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def cover(seed, world):
+    """(plan, expected blob per rank), computed once and left unchanged"""
+    from tests.mixed_plan import expected_cover, make_cover_plan
+    plan = make_cover_plan(seed, world)
+    want = expected_cover(plan, world)
+    for w in want:
+        w.setflags(write=False)
+    return plan, want
+
+
+def device_steps(plan):
+    return [s for s in plan if s["kind"] != "host"]
+
+
+def test_cover_plan_is_deterministic_per_seed():
+    from tests.mixed_plan import make_cover_plan
+    a, b, c = make_cover_plan(21, 3), make_cover_plan(21, 3), make_cover_plan(23, 3)
+    assert a == b == cover(21, 3)[0]
+    assert [s["kind"] for s in a] != [s["kind"] for s in c]                      # another walk
+    assert [(s["dtype"], s["op"], s["count"]) for s in a] != [(s["dtype"], s["op"], s["count"]) for s in c]
+
+
+@pytest.mark.parametrize("seed,world", COVER_CASES + [(24, 2)])
+def test_cover_plan_has_every_ordered_pair_once(seed, world):
+    """The walk is an Eulerian circuit of the complete directed graph on
+    LAUNCH_KINDS, self-loops included: K^2 + 1 device launches, every ordered
+    pair adjacent exactly once (host calls only sit in between), closed."""
+    from tests.mixed_plan import LAUNCH_KINDS, make_cover_plan
+    K = len(LAUNCH_KINDS)
+    assert K == 15 and len(set(LAUNCH_KINDS)) == K
+    plan = make_cover_plan(seed, world)
+    dev = device_steps(plan)
+    assert len(dev) == K * K + 1 and dev[0]["kind"] == dev[-1]["kind"]
+    pairs = collections.Counter((a["kind"], b["kind"]) for a, b in zip(dev, dev[1:]))
+    assert set(pairs) == {(a, b) for a in LAUNCH_KINDS for b in LAUNCH_KINDS}
+    assert set(pairs.values()) == {1}
+    # one host call after every 8th launch, never two in a row
+    hosts = [k for k, s in enumerate(plan) if s["kind"] == "host"]
+    assert len(hosts) == (K * K + 1) // 8 and all(b - a == 9 for a, b in zip(hosts, hosts[1:]))
+    assert len(device_steps(make_cover_plan(seed, world, host_every=3))) == K * K + 1
+
+
+@pytest.mark.parametrize("world", [2, 3, 4])
+def test_cover_expected_blob_has_the_offsets_size_on_every_rank(world):
+    from tests.mixed_plan import cover_offsets
+    plan, want = cover({2: 24, 3: 21, 4: 22}[world], world)
+    offs = cover_offsets(plan)
+    assert len(offs) == len(plan) + 1 and offs[0] == 0 and all(a <= b for a, b in zip(offs, offs[1:]))
+    assert len(want) == world
+    for r in range(world):
+        assert want[r].size == offs[-1], (world, r)
+    # reduce-scatter, rooted reduce, scan and all-to-all leave different bytes on different ranks
+    assert want[0].tobytes() != want[1].tobytes()
+
+
+def test_cover_plan_alltoallv_matrices():
+    """Every segment fits one launch (RdcPlanAlltoallCap through the C ABI, for
+    the GPU test's scratch size); the committed seeds hold an all-zero matrix
+    and one with a rank that neither sends nor receives; offsets have gaps."""
+    from rdc_amd._lib import _LIB
+    from tests.mixed_plan import COVER_SCRATCH, a2av_layout
+    zeros = idle = 0
+    for seed, world in COVER_CASES:
+        cap = ctypes.c_uint64()
+        assert _LIB.RdcPlanAlltoallCap(world, COVER_SCRATCH, ctypes.byref(cap)) == 0
+        steps = [s for s in cover(seed, world)[0] if s["kind"] == "alltoallv"]
+        assert len(steps) >= 15
+        for s in steps:
+            M = s["M"]
+            assert len(M) == world and all(len(row) == world for row in M)
+            assert all(0 <= x <= cap.value for row in M for x in row), s
+            assert s["sgap"] >= 1 and s["rgap"] >= 1
+            rows, rtotal = a2av_layout(M, s["sgap"], s["rgap"])
+            for r, (soff, slen, stotal, roff, rlen) in enumerate(rows):
+                assert slen == M[r] and rlen == [M[p][r] for p in range(world)]
+                assert all(soff[p] + slen[p] < soff[p + 1] for p in range(world - 1))     # a gap, no overlap
+                assert all(roff[p] + rlen[p] < roff[p + 1] for p in range(world - 1))
+                assert soff[-1] + slen[-1] <= stotal and roff[-1] + rlen[-1] <= rtotal == s["out"]
+            if not any(x for row in M for x in row):
+                zeros += 1
+            elif any(not any(M[r]) and not any(row[r] for row in M) for r in range(world)):
+                idle += 1
+        for s in cover(seed, world)[0]:
+            if s["kind"] == "alltoall":
+                assert 0 < s["bytes"] <= cap.value
+    assert zeros >= 1 and idle >= 1, (zeros, idle)
+
+
+def test_cover_plan_draws_every_dtype_op_count_and_offset():
+    from tests.mixed_plan import (COVER_COUNTS, COVER_PAIRS, DIRECT_BUFFER, COVER_ESZ, LOC_PAIRS, PAIRS, REDUCING)
+    assert set(COVER_PAIRS) >= set(PAIRS) | {(6, 8), (10, 8), (0, 8), (3, 9), (5, 10)}
+    assert LOC_PAIRS == [(12, 4), (13, 5)]
+    seen, counts, offs, loc_kinds = set(), set(), set(), set()
+    for seed, world in COVER_CASES:
+        for s in device_steps(cover(seed, world)[0]):
+            seen.add((s["dtype"], s["op"]))
+            offs.add(s["off"])
+            if s["dtype"] in (12, 13):
+                assert s["kind"] in REDUCING, s
+                loc_kinds.add(s["kind"])
+            if s["kind"] == "direct":
+                assert s["count"] * COVER_ESZ[s["dtype"]] == DIRECT_BUFFER + COVER_ESZ[s["dtype"]] and s["algo"] == 0
+            elif s["kind"] in ("mesh", "ring", "mesh_pull", "oneshot") and s["count"] == 2:
+                assert COVER_ESZ[s["dtype"]] == 1          # a 1-byte buffer would take the tree order instead
+            else:
+                counts.add(s["count"])
+                assert s["count"] in COVER_COUNTS
+            if s["kind"] == "coalesced":
+                assert 2 <= len(s["counts"]) <= 6 and s["counts"][0] and s["counts"][1] and s["algo"] in (0, 1, 2, 5)
+            if s["kind"] in ("bcast", "rooted"):
+                assert 0 <= s["root"] < world
+    assert seen == set(COVER_PAIRS + LOC_PAIRS)
+    assert counts == set(COVER_COUNTS) and offs == {0, 1}
+    assert loc_kinds == set(REDUCING)
+
+
+def test_cover_expected_float_data_has_no_nan():
+    """The blob is compared byte for byte, so no floating-point step's expected
+    data may hold a NaN (expected_cover asserts it step by step; this checks
+    the blobs themselves).  Pair steps are exempt: their elements move whole."""
+    from tests import ops_ref
+    from tests.mixed_plan import cover_offsets, is_float_step
+    checked = 0
+    for seed, world in COVER_CASES:
+        plan, want = cover(seed, world)
+        offs = cover_offsets(plan)
+        for k, s in enumerate(plan):
+            if is_float_step(s):
+                for r in range(world):
+                    a = np.frombuffer(want[r][offs[k]: offs[k + 1]].tobytes(), dtype=O.NP_DTYPE[s["dtype"]])
+                    assert not ops_ref.is_nan(a, s["dtype"]).any(), (seed, k, s, r)
+                checked += 1
+    assert checked > 100
+
+
+def test_cover_mismatch_is_reported_as_a_step_and_a_rank():
+    from tests.mixed_plan import cover_offsets, describe, first_mismatch, mismatch_report
+    plan, want = cover(21, 3)
+    offs = cover_offsets(plan)
+    assert mismatch_report(plan, 0, want[0].copy(), want[0]) is None
+    for k in (0, 57, len(plan) - 1):
+        assert plan[k]["out"] > 0
+        for byte in (0, plan[k]["out"] - 1):
+            got = want[2].copy()
+            got[offs[k] + byte] ^= 0x40
+            assert first_mismatch(plan, got, want[2]) == (k, byte, 1)
+            msg = mismatch_report(plan, 2, got, want[2])
+            prev = [j for j in range(k) if plan[j]["kind"] != "host"]
+            assert msg.startswith("step %d [%s] after step " % (k, describe(plan[k]))), msg
+            if prev:
+                assert "after step %d [%s]" % (prev[-1], describe(plan[prev[-1]])) in msg, msg
+            assert "rank 2 differs at 1 of %d bytes, first at byte %d of the step" % (plan[k]["out"], byte) in msg, msg
 
 
 @pytest.mark.parametrize("want,per_cu,cus,share,expect", [
