@@ -43,16 +43,37 @@ static const std::string kMainCommName = "main";
 
 /*! \brief a (value, index) pair for op::MaxLoc / op::MinLoc (MI355X addition;
  *  MPI_FLOAT_INT / MPI_2INT): "which rank holds the best candidate, and where".
- *  8 bytes, 8-byte aligned (the library refuses a pair buffer that is only
- *  4-byte aligned), V = float or int32_t.  There is no 16-byte
- *  { double, int64 } pair. */
+ *  V = float or int32_t: 8 bytes, 8-byte aligned, an int32_t index (the library
+ *  refuses a pair buffer that is only 4-byte aligned).
+ *  V = double or int64_t: 16 bytes, 16-byte aligned, an int64_t index — the
+ *  index type follows the value's width, so it can number every element the
+ *  library can move (dtypes 16 / 17; the library refuses a buffer of them that
+ *  is only 8-byte aligned).  There is no padded { double, int32 } pair
+ *  (MPI_DOUBLE_INT: its padding bytes have no defined bits) and no
+ *  { float, int64 } pair. */
 template <typename V>
 struct alignas(8) ValueIndex {
     static_assert(std::is_same<V, float>::value || std::is_same<V, int32_t>::value,
-                  "rdc::ValueIndex<V>: V is float or int32_t");
+                  "rdc::ValueIndex<V>: V is float, int32_t, double or int64_t");
     V value;
     int32_t index;
 };
+template <>
+struct alignas(16) ValueIndex<double> {
+    double value;
+    int64_t index;
+};
+template <>
+struct alignas(16) ValueIndex<int64_t> {
+    int64_t value;
+    int64_t index;
+};
+static_assert(sizeof(ValueIndex<double>) == 16 && alignof(ValueIndex<double>) == 16 &&
+                  std::is_trivially_copyable<ValueIndex<double>>::value,
+              "rdc::ValueIndex<double> is the 16-byte element of dtype 16");
+static_assert(sizeof(ValueIndex<int64_t>) == 16 && alignof(ValueIndex<int64_t>) == 16 &&
+                  std::is_trivially_copyable<ValueIndex<int64_t>>::value,
+              "rdc::ValueIndex<int64_t> is the 16-byte element of dtype 17");
 static_assert(sizeof(ValueIndex<float>) == 8 && alignof(ValueIndex<float>) == 8 &&
                   std::is_trivially_copyable<ValueIndex<float>>::value,
               "rdc::ValueIndex<float> is the 8-byte element of dtype 12");
@@ -89,7 +110,10 @@ enum DataType {
     kULongLong = 9,
     /*! \brief MI355X additions: ValueIndex<float>, ValueIndex<int32_t> (MPI_FLOAT_INT / MPI_2INT) */
     kFloatInt = 12,
-    kIntInt = 13
+    kIntInt = 13,
+    /*! \brief ValueIndex<double>, ValueIndex<int64_t>: 16-byte pairs (14 and 15 are unassigned) */
+    kDoubleInt64 = 16,
+    kInt64Int64 = 17
 };
 template <typename DType>
 inline DataType GetType(void);
@@ -106,6 +130,8 @@ template <> inline DataType GetType<long long>(void) { return kLongLong; }      
 template <> inline DataType GetType<unsigned long long>(void) { return kULongLong; }    // NOLINT
 template <> inline DataType GetType<ValueIndex<float>>(void) { return kFloatInt; }
 template <> inline DataType GetType<ValueIndex<int32_t>>(void) { return kIntInt; }
+template <> inline DataType GetType<ValueIndex<double>>(void) { return kDoubleInt64; }
+template <> inline DataType GetType<ValueIndex<int64_t>>(void) { return kInt64Int64; }
 }  // namespace mpi
 
 namespace detail {

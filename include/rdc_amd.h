@@ -17,13 +17,22 @@
  *       0 int8, 1 uint8, 2 int32, 3 uint32, 4 int64, 5 uint64, 6 float32,
  *       7 float64, 8 long long, 9 unsigned long long
  *     MI355X additions: 10 float16 (IEEE binary16), 11 bfloat16, and the
- *     (value, index) pairs of MAXLOC / MINLOC, 8 bytes, the value first:
+ *     (value, index) pairs of MAXLOC / MINLOC, the value first, 8 bytes:
  *       12 F32_I32 { float value; int32_t index; }
  *       13 I32_I32 { int32_t value; int32_t index; }
- *     A buffer of pairs must be 8-byte aligned.  The C struct alone guarantees
- *     4 (declare it alignas(8), as rdc::ValueIndex<V> is): a 4-byte aligned
- *     pair buffer is refused as "not aligned to its element size".  There is no
- *     16-byte { double, int64 } pair.
+ *     or 16 bytes (a 64-bit index numbers every element the library can move;
+ *     float64 scores keep their bits):
+ *       16 F64_I64 { double value; int64_t index; }
+ *       17 I64_I64 { int64_t value; int64_t index; }
+ *     A buffer of pairs, host or device, must be aligned to the pair's size: 8
+ *     bytes for 12 / 13, 16 bytes for 16 / 17.  The C struct alone guarantees 4
+ *     / 8 (declare it alignas(8) / alignas(16), as rdc::ValueIndex<V> is): a
+ *     less aligned pair buffer is refused as "not aligned to its element
+ *     size" before anything is launched; for 16 / 17 RdcAllreduce refuses it
+ *     at a world size of 1 too.  Codes 14 and 15 are unassigned and refused as
+ *     "bad dtype 14" / "bad dtype 15".  Not covered: the padded
+ *     { double, int32 } of MPI_DOUBLE_INT, whose padding bytes have no defined
+ *     bits, and a { float, int64 } pair.
  *   - op: mpi::OpType (include/core/mpi.h:12-17) = rdc/core.py:16-20:
  *       0 MAX, 1 MIN, 2 SUM, 3 BITOR (integer dtypes only)
  *     MI355X additions (MPI_MAXLOC / MPI_MINLOC): 4 MAXLOC, 5 MINLOC.
@@ -34,10 +43,13 @@
  *     MAX / MIN; -0.0f == +0.0f is a tie in value and the lower index wins; on
  *     a full tie (equal value, equal index) dst stays whole, value bits
  *     included, so a +0 / -0 pair with equal indexes depends on the operand
- *     order, as NaN does for MAX.  MAXLOC / MINLOC are valid with dtypes 12 /
- *     13 only, and those dtypes with MAXLOC / MINLOC only: every other
- *     combination is refused before anything is launched, the message naming
- *     both.  RdcFill refuses the pair dtypes (upload the inputs).
+ *     order, as NaN does for MAX.  On 16 / 17 the comparisons are IEEE double
+ *     and signed 64-bit, on all 64 bits of value and index.  MAXLOC / MINLOC
+ *     are valid with dtypes 12, 13, 16 and 17 only, and those dtypes with
+ *     MAXLOC / MINLOC only: every other combination is refused before anything
+ *     is launched, the message naming both.  RdcFill has no pattern for the
+ *     pair dtypes and refuses them (upload the inputs); RdcCommAutotune times
+ *     no pair candidates and refuses them too.
  *     MI355X additions (MPI_PROD / MPI_BAND / MPI_BXOR), dst = OP(dst, src):
  *       8 PROD   dst * src   every arithmetic dtype 0-11
  *       9 BITAND dst & src   integer dtypes only, as BITOR

@@ -58,6 +58,7 @@ _ALGOS = {"auto": ALGO_AUTO, "ring": ALGO_RING, "mesh": ALGO_MESH, "oneshot": AL
 
 _OP_LOC = (4, 5)  # Op.MAXLOC, Op.MINLOC
 _PAIR_CODES = {"float32": 12, "int32": 13}  # value type -> F32_I32 / I32_I32
+_PAIR16_CODES = {"float64": 16, "int64": 17}  # value type -> F64_I64 / I64_I64
 
 
 def _elem_args(tensor, op, value):
@@ -65,15 +66,24 @@ def _elem_args(tensor, op, value):
     struct dtype, so Op.MAXLOC / Op.MINLOC take their (value, index) pairs as
     a ``torch.int32`` tensor whose last dimension is 2 (``pack_pairs``), the
     value's bits first; ``value`` ("float32", the default, or "int32") says how
-    to read them.  Anything else raises TypeError before the library is called."""
+    to read them.  The 16-byte pairs are a ``torch.int64`` tensor of the same
+    shape (``pack_pairs16``) and need an explicit ``value`` ("float64" or
+    "int64"): an int64 tensor alone never selects them.  Anything else raises
+    TypeError before the library is called."""
     if int(op) in _OP_LOC:
         import torch
+        if tensor.dtype == torch.int64 and value in _PAIR16_CODES:
+            if tensor.dim() < 1 or tensor.shape[-1] != 2:
+                raise TypeError("rdc_amd: MAXLOC / MINLOC with value=%r take a torch.int64 tensor whose last "
+                                "dimension is 2 (value bits, index), got %s" % (value, tuple(tensor.shape)))
+            return tensor.numel() // 2, _PAIR16_CODES[value]
         if tensor.dtype != torch.int32 or tensor.dim() < 1 or tensor.shape[-1] != 2:
             raise TypeError("rdc_amd: MAXLOC / MINLOC take a torch.int32 tensor whose last dimension is 2 "
-                            "(value bits, index), got %s %s" % (tensor.dtype, tuple(tensor.shape)))
+                            "(value bits, index), or a torch.int64 one with value=\"float64\" | \"int64\", "
+                            "got %s %s" % (tensor.dtype, tuple(tensor.shape)))
         v = "float32" if value is None else value
         if v not in _PAIR_CODES:
-            raise TypeError("rdc_amd: value must be \"float32\" or \"int32\", got %r" % (value,))
+            raise TypeError("rdc_amd: value must be \"float32\" or \"int32\" for an int32 tensor, got %r" % (value,))
         return tensor.numel() // 2, _PAIR_CODES[v]
     if value is not None:
         raise TypeError("rdc_amd: value= goes with Op.MAXLOC / Op.MINLOC only")
@@ -140,7 +150,8 @@ class Comm(object):
         (rdc::Allreduce<OP>(buf, count, comm_name), include/api.h:62-64) and
         returns the reduced flat array.  Op.MAXLOC / Op.MINLOC: an int32
         tensor of (value bits, index) pairs, last dimension 2, read as
-        ``value`` = "float32" (default) or "int32" (``_elem_args``); so for
+        ``value`` = "float32" (default) or "int32", or an int64 tensor of
+        16-byte pairs with ``value`` = "float64" or "int64" (``_elem_args``); so for
         reduce_scatter, reduce, scan and allreduce_coalesced."""
         if not _is_tensor(tensor):
             from .core import host_allreduce

@@ -50,6 +50,11 @@ class Op(Enum):
 # Tensors: torch.int32 [..., 2] with value="float32" | "int32" (Comm.allreduce).
 F32_I32 = np.dtype([("value", np.float32), ("index", np.int32)])
 I32_I32 = np.dtype([("value", np.int32), ("index", np.int32)])
+# the 16-byte pairs: a 64-bit index (it can number every element the library
+# moves) and float64 / int64 values; arrays must be 16-byte aligned.
+# Tensors: torch.int64 [..., 2] with an explicit value="float64" | "int64".
+F64_I64 = np.dtype([("value", np.float64), ("index", np.int64)])
+I64_I64 = np.dtype([("value", np.int64), ("index", np.int64)])
 
 DTYPE_ENUM__ = {
     np.dtype("int8"): 0,
@@ -63,8 +68,10 @@ DTYPE_ENUM__ = {
     np.dtype("float16"): 10,
     F32_I32: 12,
     I32_I32: 13,
+    F64_I64: 16,
+    I64_I64: 17,
 }
-_PAIR_DTYPES = (F32_I32, I32_I32)
+_PAIR_DTYPES = (F32_I32, I32_I32, F64_I64, I64_I64)
 
 
 def init(args=None, lib="standard", lib_dll=None):
@@ -148,8 +155,9 @@ def allreduce(data, op, prepare_fun=None, value=None):
     gave a view of ``data`` — the reference's rule, rdc/core.py:196-217).
     torch.Tensor on a ROCm device: reduced in place on the GPU and returned.
     ``prepare_fun(data)``, if given, runs before the reduction.
-    Op.MAXLOC / Op.MINLOC: a structured array of dtype F32_I32 / I32_I32, or
-    an int32 tensor of pairs read as ``value`` (Comm.allreduce).
+    Op.MAXLOC / Op.MINLOC: a structured array of dtype F32_I32 / I32_I32 /
+    F64_I64 / I64_I64, or an int32 / int64 tensor of pairs read as ``value``
+    (Comm.allreduce).
     """
     op = int(Op(op) if not isinstance(op, Op) else op)
     if type(data).__module__.startswith("torch"):
@@ -167,7 +175,7 @@ def host_allreduce(data, op, prepare_fun=None, comm=None):
     if not isinstance(data, np.ndarray):
         raise TypeError("allreduce only takes in numpy.ndarray or torch.Tensor")
     buf = data.ravel()
-    misaligned_pairs = buf.dtype in _PAIR_DTYPES and buf.ctypes.data % 8 != 0
+    misaligned_pairs = buf.dtype in _PAIR_DTYPES and buf.ctypes.data % buf.dtype.itemsize != 0
     if buf.base is data.base and not misaligned_pairs:  # those go to the library as they are: it refuses them
         buf = buf.copy()
     if buf.dtype not in DTYPE_ENUM__:

@@ -352,11 +352,12 @@ void check_dtype_op(int dtype, int op) {
     if (rdc_op_is_loc(op) != rdc_dtype_is_pair(dtype))
         throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
                                     std::to_string(op) + "): MAXLOC / MINLOC go with the pair dtypes F32_I32 / "
-                                    "I32_I32 only");
+                                    "I32_I32 / F64_I64 / I64_I64 only");
 }
 
-// host buffers of (value, index) pairs: 8-byte aligned like device ones (the
-// staged copies would hide a 4-byte aligned buffer from the device path's check)
+// host buffers of (value, index) pairs: aligned to the pair's size (8 or 16
+// bytes) like device ones (the staged copies would hide a less aligned buffer
+// from the device path's check)
 void check_pair_aligned(const void* p, int dtype) {
     if (rdc_dtype_is_pair(dtype) && (uintptr_t)p % rdc_dtype_size(dtype))
         throw std::invalid_argument("rdc: buffer not aligned to its element size");
@@ -365,6 +366,9 @@ void check_pair_aligned(const void* p, int dtype) {
 // synchronous allreduce of host or device memory on communicator c
 void allreduce_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, int dtype, int op) {
     check_dtype_op(dtype, op);
+    // a 16-byte pair's alignment is more than its C struct guarantees: refused
+    // at every world size, so a caller meets the rule before it scales out
+    if (rdc_dtype_size(dtype) == 16) check_pair_aligned(sendrecv, dtype);
     if (c->size() == 1 || count == 0) return;
     hipStream_t s = manager_stream(m, c->device());
     if (is_device_pointer(sendrecv)) {
@@ -738,6 +742,8 @@ int RdcAllreduce(void* sendrecv, size_t count, int dtype, int op, void (*prepare
         require_init(m);
         if (prepare_fun) prepare_fun(prepare_arg);
         check_dtype_op(dtype, op);
+        // (a 16-byte pair buffer's alignment is checked at every world size: allreduce_sync)
+        if (rdc_dtype_size(dtype) == 16) check_pair_aligned(sendrecv, dtype);
         // world size 1: Communicator::Allreduce returns at once (communicator_base.h:133-138)
         if (m.world == 1 || count == 0) return;
         allreduce_sync(m, get_comm(m, "main", true), sendrecv, count, dtype, op);

@@ -23,7 +23,19 @@ enum {
     // aligned one is refused like any buffer not aligned to its element size.
     RDC_DT_F32_I32 = 12,  // { float value; int32_t index; }
     RDC_DT_I32_I32 = 13,  // { int32_t value; int32_t index; }
-    RDC_DT_COUNT = 14
+    // codes 14 and 15 are unassigned and refused ("bad dtype 14"): callers use
+    // 14 as their example of an unknown dtype
+    RDC_DT_UNASSIGNED_14 = 14,
+    RDC_DT_UNASSIGNED_15 = 15,
+    // the 16-byte pairs: a 64-bit value and a 64-bit index, so the index can
+    // address every element the library can move and float64 scores keep
+    // their bits.  Buffers of them must be 16-byte aligned (the C struct alone
+    // guarantees 8): one element is one 16-byte vector of the device path.
+    // Not covered: MPI_DOUBLE_INT's padded { double, int32 } (its padding has
+    // no defined bits) and a { float, int64 } pair.
+    RDC_DT_F64_I64 = 16,  // { double value; int64_t index; }
+    RDC_DT_I64_I64 = 17,  // { int64_t value; int64_t index; }
+    RDC_DT_COUNT = 18     // one past the last code; 14 and 15 inside it are not dtypes (rdc_dtype_size = 0)
 };
 // mpi::OpType (include/core/mpi.h:12-17)
 // + MI355X-build additions MAXLOC / MINLOC (MPI_MAXLOC / MPI_MINLOC), valid
@@ -125,11 +137,14 @@ static inline size_t rdc_dtype_size(int dtype) {
         case RDC_DT_INT64: case RDC_DT_UINT64: case RDC_DT_FLOAT64:
         case RDC_DT_LONGLONG: case RDC_DT_ULONGLONG: return 8;
         case RDC_DT_F32_I32: case RDC_DT_I32_I32: return 8;
+        case RDC_DT_F64_I64: case RDC_DT_I64_I64: return 16;
         case RDC_DT_FLOAT16: case RDC_DT_BFLOAT16: return 2;
         default: return 0;
     }
 }
-static inline int rdc_dtype_is_pair(int dtype) { return dtype == RDC_DT_F32_I32 || dtype == RDC_DT_I32_I32; }
+static inline int rdc_dtype_is_pair(int dtype) {
+    return dtype == RDC_DT_F32_I32 || dtype == RDC_DT_I32_I32 || dtype == RDC_DT_F64_I64 || dtype == RDC_DT_I64_I64;
+}
 static inline int rdc_op_is_loc(int op) { return op == RDC_OP_MAXLOC || op == RDC_OP_MINLOC; }
 // false for the pair dtypes: no arithmetic is defined on them
 static inline int rdc_dtype_is_float(int dtype) {

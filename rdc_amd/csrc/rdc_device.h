@@ -138,11 +138,33 @@ struct alignas(8) pair_i32_t {
 };
 static_assert(sizeof(pair_f32_t) == 8 && std::is_trivially_copyable<pair_f32_t>::value, "pair_f32_t");
 static_assert(sizeof(pair_i32_t) == 8 && std::is_trivially_copyable<pair_i32_t>::value, "pair_i32_t");
+// the 16-byte pairs (RDC_DT_F64_I64 / RDC_DT_I64_I64): one element per 16-byte
+// vector, buffers 16-byte aligned, so every chunk, tile and piece of them
+// starts on a vector boundary and the element-wise heads and tails are empty;
+// where an element-wise path does run (ld_elem_sys / st_elem_wt) an element
+// moves as two 64-bit words
+struct alignas(16) pair_f64_t {
+    double value;
+    int64_t index;
+};
+struct alignas(16) pair_i64_t {
+    int64_t value;
+    int64_t index;
+};
+static_assert(sizeof(pair_f64_t) == 16 && std::is_trivially_copyable<pair_f64_t>::value, "pair_f64_t");
+static_assert(sizeof(pair_i64_t) == 16 && std::is_trivially_copyable<pair_i64_t>::value, "pair_i64_t");
 
 // does src replace dst?  Non-short-circuit on purpose: two compares, one
 // and, one or, no branch.
 template <bool MAX, typename V>
 __device__ __forceinline__ bool loc_take(V dv, int32_t di, V sv, int32_t si) {
+    const bool better = MAX ? (dv < sv) : (dv > sv);
+    return better | ((dv == sv) & (si < di));
+}
+// the same on a 64-bit index (the 16-byte pairs); an overload, so the 8-byte
+// pairs' calls resolve as before
+template <bool MAX, typename V>
+__device__ __forceinline__ bool loc_take(V dv, int64_t di, V sv, int64_t si) {
     const bool better = MAX ? (dv < sv) : (dv > sv);
     return better | ((dv == sv) & (si < di));
 }
@@ -152,6 +174,11 @@ template <> struct OpF<RDC_OP_MAXLOC> {
     }
     __device__ __forceinline__ static pair_i32_t apply(pair_i32_t d, pair_i32_t s) {
         return loc_take<true>(d.value, d.index, s.value, s.index) ? s : d;
+    }    __device__ __forceinline__ static pair_f64_t apply(pair_f64_t d, pair_f64_t s) {
+        return loc_take<true>(d.value, d.index, s.value, s.index) ? s : d;
+    }
+    __device__ __forceinline__ static pair_i64_t apply(pair_i64_t d, pair_i64_t s) {
+        return loc_take<true>(d.value, d.index, s.value, s.index) ? s : d;
     }
 };
 template <> struct OpF<RDC_OP_MINLOC> {
@@ -159,6 +186,11 @@ template <> struct OpF<RDC_OP_MINLOC> {
         return loc_take<false>(d.value, d.index, s.value, s.index) ? s : d;
     }
     __device__ __forceinline__ static pair_i32_t apply(pair_i32_t d, pair_i32_t s) {
+        return loc_take<false>(d.value, d.index, s.value, s.index) ? s : d;
+    }    __device__ __forceinline__ static pair_f64_t apply(pair_f64_t d, pair_f64_t s) {
+        return loc_take<false>(d.value, d.index, s.value, s.index) ? s : d;
+    }
+    __device__ __forceinline__ static pair_i64_t apply(pair_i64_t d, pair_i64_t s) {
         return loc_take<false>(d.value, d.index, s.value, s.index) ? s : d;
     }
 };
@@ -298,6 +330,32 @@ __device__ __forceinline__ v4u reduce16<RDC_OP_MAXLOC, pair_i32_t>(v4u d, v4u s)
 template <>
 __device__ __forceinline__ v4u reduce16<RDC_OP_MINLOC, pair_i32_t>(v4u d, v4u s) { return loc16::reduce<false, false>(d, s); }
 
+// the 16-byte pairs, one per vector: the 64-bit value from dwords 0-1 and the
+// 64-bit index from dwords 2-3, compared on all 64 bits (v_cmp_*_f64 or
+// v_cmp_*_i64 x2 on the value, v_cmp_lt_i64 on the index), and all four dwords
+// selected under the one condition
+namespace loc16 {
+template <bool MAX, bool FLOAT>
+__device__ __forceinline__ v4u reduce_wide(v4u d, v4u s) {
+    const uint64_t dvb = ((uint64_t)d[1] << 32) | d[0], svb = ((uint64_t)s[1] << 32) | s[0];
+    const int64_t di = (int64_t)(((uint64_t)d[3] << 32) | d[2]), si = (int64_t)(((uint64_t)s[3] << 32) | s[2]);
+    const bool take = FLOAT ? loc_take<MAX>(__builtin_bit_cast(double, dvb), di, __builtin_bit_cast(double, svb), si)
+                            : loc_take<MAX>((int64_t)dvb, di, (int64_t)svb, si);
+    v4u out;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[k] = take ? s[k] : d[k];
+    return out;
+}
+}  // namespace loc16
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_MAXLOC, pair_f64_t>(v4u d, v4u s) { return loc16::reduce_wide<true, true>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_MINLOC, pair_f64_t>(v4u d, v4u s) { return loc16::reduce_wide<false, true>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_MAXLOC, pair_i64_t>(v4u d, v4u s) { return loc16::reduce_wide<true, false>(d, s); }
+template <>
+__device__ __forceinline__ v4u reduce16<RDC_OP_MINLOC, pair_i64_t>(v4u d, v4u s) { return loc16::reduce_wide<false, false>(d, s); }
+
 // ------------------------------------------------------- memory access ----
 __device__ __forceinline__ v4u ld16(const void* p) { return *reinterpret_cast<const v4u*>(p); }
 __device__ __forceinline__ void st16(void* p, v4u v) { *reinterpret_cast<v4u*>(p) = v; }
@@ -334,13 +392,23 @@ template <typename W>
 __device__ __forceinline__ void st_wt(W* p, W v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-// one element of type T (any 1/2/4/8-byte type) written through
+// one element of type T (any 1/2/4/8-byte type) written through; a 16-byte
+// element (the wide pairs) as two 64-bit words, each written through: there is
+// no 128-bit atomic, and an element seen half-written is harmless because every
+// hand-off is ordered by its flag, stored after both words were performed
 template <typename T>
 __device__ __forceinline__ void st_elem_wt(void* p, T v) {
-    typedef typename std::conditional<sizeof(T) == 1, uint8_t,
-            typename std::conditional<sizeof(T) == 2, uint16_t,
-            typename std::conditional<sizeof(T) == 4, uint32_t, uint64_t>::type>::type>::type W;
-    st_wt(reinterpret_cast<W*>(p), __builtin_bit_cast(W, v));
+    if constexpr (sizeof(T) == 16) {
+        uint64_t w[2];
+        __builtin_memcpy(w, &v, 16);
+        st_wt(reinterpret_cast<uint64_t*>(p), w[0]);
+        st_wt(reinterpret_cast<uint64_t*>(p) + 1, w[1]);
+    } else {
+        typedef typename std::conditional<sizeof(T) == 1, uint8_t,
+                typename std::conditional<sizeof(T) == 2, uint16_t,
+                typename std::conditional<sizeof(T) == 4, uint32_t, uint64_t>::type>::type>::type W;
+        st_wt(reinterpret_cast<W*>(p), __builtin_bit_cast(W, v));
+    }
 }
 
 // Where a block_copy writes: this GPU's own memory (user buffers, local
@@ -360,13 +428,22 @@ template <typename W>
 __device__ __forceinline__ W ld_sys(const W* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-// one element of type T (any 1/2/4/8-byte type) read at system scope
+// one element of type T (any 1/2/4/8-byte type) read at system scope; a
+// 16-byte element as two 64-bit system-scope loads (st_elem_wt's twin)
 template <typename T>
 __device__ __forceinline__ T ld_elem_sys(const void* p) {
-    typedef typename std::conditional<sizeof(T) == 1, uint8_t,
-            typename std::conditional<sizeof(T) == 2, uint16_t,
-            typename std::conditional<sizeof(T) == 4, uint32_t, uint64_t>::type>::type>::type W;
-    return __builtin_bit_cast(T, ld_sys(reinterpret_cast<const W*>(p)));
+    if constexpr (sizeof(T) == 16) {
+        const uint64_t w[2] = {ld_sys(reinterpret_cast<const uint64_t*>(p)),
+                               ld_sys(reinterpret_cast<const uint64_t*>(p) + 1)};
+        T v;
+        __builtin_memcpy(&v, w, 16);
+        return v;
+    } else {
+        typedef typename std::conditional<sizeof(T) == 1, uint8_t,
+                typename std::conditional<sizeof(T) == 2, uint16_t,
+                typename std::conditional<sizeof(T) == 4, uint32_t, uint64_t>::type>::type>::type W;
+        return __builtin_bit_cast(T, ld_sys(reinterpret_cast<const W*>(p)));
+    }
 }
 
 // ------------------------------------------------------------- hand-off ----

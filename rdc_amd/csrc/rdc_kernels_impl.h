@@ -1118,11 +1118,21 @@ __device__ void block_scan_fold(char* own, const char* recv, char* fwd, uint64_t
     const unsigned tid = threadIdx.x;
     const bool push = fwd != nullptr;
     auto fold_elem = [&](uint64_t e) {
-        T* d = reinterpret_cast<T*>(own + e);
-        const T y = ld_elem_sys<T>(recv + e);
-        const T p = OpF<OP>::apply(y, *d);
-        *d = exclusive ? y : p;
-        if (push) st_elem_wt<T>(fwd + e, p);
+        if constexpr (sizeof(T) == 16) {
+            // a 16-byte pair is one vector: folded and selected as v4u (a
+            // run-time choice between two structs would live in scratch memory)
+            v4u* d = reinterpret_cast<v4u*>(own + e);
+            const v4u y = __builtin_bit_cast(v4u, ld_elem_sys<T>(recv + e));
+            const v4u p = reduce16<OP, T>(y, *d);
+            *d = exclusive ? y : p;
+            if (push) st_elem_wt<T>(fwd + e, __builtin_bit_cast(T, p));
+        } else {
+            T* d = reinterpret_cast<T*>(own + e);
+            const T y = ld_elem_sys<T>(recv + e);
+            const T p = OpF<OP>::apply(y, *d);
+            *d = exclusive ? y : p;
+            if (push) st_elem_wt<T>(fwd + e, p);
+        }
     };
     if ((((uintptr_t)own ^ (uintptr_t)recv) & 15) != 0) {  // buffer not 16-B aligned: element-wise
         for (uint64_t e = (uint64_t)tid * sizeof(T); e < len; e += (uint64_t)kBlock * sizeof(T)) fold_elem(e);
@@ -1746,7 +1756,8 @@ __device__ __forceinline__ bool ll_match(const v4u& lo, const v4u& hi, uint32_t 
 // what the attribute is for.
 template <typename T, int NMAX, int BS, bool HX>
 struct SvcWaves {
-    static constexpr bool kPair = std::is_same<T, pair_f32_t>::value || std::is_same<T, pair_i32_t>::value;
+    static constexpr bool kPair = std::is_same<T, pair_f32_t>::value || std::is_same<T, pair_i32_t>::value ||
+                                  std::is_same<T, pair_f64_t>::value || std::is_same<T, pair_i64_t>::value;
     static constexpr int kMin = (kPair && NMAX == 16 && BS == 256 && HX) ? 2 : BS / 256;
 };
 template <int OP, typename T, int NMAX, int BS, bool HX>
@@ -1754,9 +1765,11 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(SvcWaves<T, 
 void k_svc(SvcArgs a) {
     constexpr int L = 16 / sizeof(T);  // elements per vector
     constexpr int U = 4;               // input vectors in flight per thread
+    // (a 16-byte element is the vector itself: L = 1, and no vector crosses a chunk boundary)
     typedef typename std::conditional<sizeof(T) == 1, uint8_t,
             typename std::conditional<sizeof(T) == 2, uint16_t,
-            typename std::conditional<sizeof(T) == 4, uint32_t, uint64_t>::type>::type>::type UT;
+            typename std::conditional<sizeof(T) == 4, uint32_t,
+            typename std::conditional<sizeof(T) == 8, uint64_t, v4u>::type>::type>::type>::type UT;
     const int n = a.n, r = a.rank;
     const unsigned tid = threadIdx.x;
     SvcBox* box = a.box;
@@ -2246,6 +2259,17 @@ inline bool pick_loc(int dtype, KernelSet* ks) {
     switch (dtype) {
         case RDC_DT_F32_I32: RDC_SET(pair_f32_t)
         case RDC_DT_I32_I32: RDC_SET(pair_i32_t)
+        default: return false;
+    }
+}
+
+// the 16-byte (value, index) pairs, instantiated in a unit of their own
+// (rdc_kernels_loc16.hip) so that the parallel build stays balanced
+template <int OP>
+inline bool pick_loc16(int dtype, KernelSet* ks) {
+    switch (dtype) {
+        case RDC_DT_F64_I64: RDC_SET(pair_f64_t)
+        case RDC_DT_I64_I64: RDC_SET(pair_i64_t)
         default: return false;
     }
 }

@@ -80,3 +80,29 @@ def unpack_pairs(pairs, value="float32"):
         raise TypeError("rdc_amd: value must be \"float32\" or \"int32\", got %r" % (value,))
     v = pairs[..., 0].contiguous()
     return (v.view(torch.float32) if value == "float32" else v), pairs[..., 1].contiguous()
+
+
+def pack_pairs16(values, indices):
+    """The 16-byte (value, index) pairs (F64_I64 / I64_I64): a contiguous
+    ``torch.int64`` tensor of shape ``values.shape + (2,)`` holding each
+    value's bits (``values``: float64 or int64) and its int64 index.  Pass it
+    with ``value="float64"`` or ``value="int64"``.  torch allocations are
+    16-byte aligned, as these pairs must be."""
+    import torch
+    if values.dtype not in (torch.float64, torch.int64):
+        raise TypeError("rdc_amd: pack_pairs16 takes float64 or int64 values, got %s" % values.dtype)
+    if indices.shape != values.shape:
+        raise ValueError("rdc_amd: pack_pairs16 needs values and indices of one shape")
+    return torch.stack((values.contiguous().view(torch.int64), indices.to(torch.int64)), dim=-1).contiguous()
+
+
+def unpack_pairs16(pairs, value):
+    """``(values, indices)`` of a tensor made by ``pack_pairs16``; ``value``
+    says how to read the value bits ("float64" or "int64")."""
+    import torch
+    if pairs.dtype != torch.int64 or pairs.dim() < 1 or pairs.shape[-1] != 2:
+        raise TypeError("rdc_amd: unpack_pairs16 takes a torch.int64 tensor whose last dimension is 2")
+    if value not in ("float64", "int64"):
+        raise TypeError("rdc_amd: value must be \"float64\" or \"int64\", got %r" % (value,))
+    v = pairs[..., 0].contiguous()
+    return (v.view(torch.float64) if value == "float64" else v), pairs[..., 1].contiguous()

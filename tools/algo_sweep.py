@@ -45,10 +45,11 @@ call and the spread.  Next to them scan_hbm_fraction = the scan's modelled HBM
 bytes (RdcPlanScanBytes, read + write, summed over the ranks: they share one
 GPU) per pipelined call over the HBM peak.
 SWEEP_DTYPE / SWEEP_OP pick the element type and operator of the allreduce,
-reduce_to and scan modes: f32 (default) / i64 / f32_i32 and sum (default) / max
-/ maxloc.  SWEEP_DTYPE=f32_i32 SWEEP_OP=maxloc times MaxLoc over (value, index)
-pairs, its inputs uploaded from numpy (RdcFill has no pattern for pairs);
-SWEEP_DTYPE=i64 SWEEP_OP=max is its yardstick at the same byte sizes.
+reduce_to and scan modes: f32 (default) / i64 / f32_i32 / f64_i64 and sum
+(default) / max / maxloc.  SWEEP_DTYPE=f32_i32 (8-byte pairs) or f64_i64
+(16-byte pairs) with SWEEP_OP=maxloc times MaxLoc over (value, index) pairs,
+its inputs uploaded from numpy (RdcFill has no pattern for pairs);
+SWEEP_DTYPE=i64 SWEEP_OP=max is their yardstick at the same byte sizes.
 
     python -m torch.distributed.run --nproc-per-node N tools/algo_sweep.py [sizes_MiB] [steps]
 """
@@ -65,7 +66,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK = 8.0e12  # bytes / s, one MI355X
 
 # element type and operator of the allreduce / reduce_to / scan modes
-DT, ESZ = {"f32": (6, 4), "i64": (4, 8), "f32_i32": (12, 8)}[os.environ.get("SWEEP_DTYPE", "f32")]
+DT, ESZ = {"f32": (6, 4), "i64": (4, 8), "f32_i32": (12, 8), "f64_i64": (16, 16)}[os.environ.get("SWEEP_DTYPE", "f32")]
 OP = {"sum": 2, "max": 0, "maxloc": 4}[os.environ.get("SWEEP_OP", "sum")]
 
 
@@ -73,7 +74,7 @@ def fill_input(buf, rank):
     """Synthetic input over the whole buffer: RdcFill, or for pairs an upload
     from numpy (values from a small set so that ranks tie, index = rank)."""
     import rdc_amd
-    if DT != 12:
+    if DT not in (12, 16):
         from rdc_amd._lib import _LIB, check_call
         import torch
         check_call(_LIB.RdcFill(ctypes.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size() // ESZ, DT,
@@ -82,8 +83,8 @@ def fill_input(buf, rank):
     import numpy as np
     import torch
     rng = np.random.default_rng(0x5EED0000 + rank)
-    x = np.empty(buf.numel() * buf.element_size() // 8, dtype=rdc_amd.F32_I32)
-    x["value"] = rng.integers(-4, 5, x.size).astype(np.float32)
+    x = np.empty(buf.numel() * buf.element_size() // ESZ, dtype=rdc_amd.F32_I32 if DT == 12 else rdc_amd.F64_I64)
+    x["value"] = rng.integers(-4, 5, x.size).astype(x.dtype["value"])
     x["index"] = rank
     buf.view(torch.uint8).copy_(torch.from_numpy(x.view(np.uint8)))
 
