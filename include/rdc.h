@@ -108,6 +108,9 @@ enum DataType {
     kDouble = 7,
     kLongLong = 8,
     kULongLong = 9,
+    /*! \brief MI355X additions: rdc::Float16 / rdc::BFloat16 (AllreduceAcc32 and its siblings) */
+    kFloat16 = 10,
+    kBFloat16 = 11,
     /*! \brief MI355X additions: ValueIndex<float>, ValueIndex<int32_t> (MPI_FLOAT_INT / MPI_2INT) */
     kFloatInt = 12,
     kIntInt = 13,
@@ -134,7 +137,24 @@ template <> inline DataType GetType<ValueIndex<double>>(void) { return kDoubleIn
 template <> inline DataType GetType<ValueIndex<int64_t>>(void) { return kInt64Int64; }
 }  // namespace mpi
 
+/*! \brief 16-bit floating elements as storage (IEEE binary16 / bfloat16 bit
+ *  patterns; the host header does no arithmetic on them): the element types
+ *  of AllreduceAcc32 / ReduceScatterAcc32 / ReduceToAcc32.  A compiler's own
+ *  16-bit type of the same layout can be passed through a pointer cast */
+struct Float16 {
+    uint16_t bits;
+};
+struct BFloat16 {
+    uint16_t bits;
+};
+static_assert(sizeof(Float16) == 2 && sizeof(BFloat16) == 2, "16-bit elements of dtypes 10 / 11");
+
 namespace detail {
+/*! \brief the element types the float32-accumulated Sum takes: anything else
+ *  (AllreduceAcc32<float>) does not compile */
+template <typename T> struct Acc32Type;
+template <> struct Acc32Type<Float16> { static const mpi::DataType kType = mpi::kFloat16; };
+template <> struct Acc32Type<BFloat16> { static const mpi::DataType kType = mpi::kBFloat16; };
 template <typename T> struct IsValueIndex : std::false_type {};
 template <typename V> struct IsValueIndex<ValueIndex<V>> : std::true_type {};
 /*! \brief MaxLoc / MinLoc fold ValueIndex<V> and nothing else folds it: a
@@ -469,6 +489,19 @@ public:
      *  is only read.  root must be the same on every rank */
     virtual void ReduceTo(void* sendrecvbuf, uint64_t count, mpi::DataType dtype, mpi::OpType op, int root) {
         detail::Check(RdcReduceToOn(handle_, sendrecvbuf, count, (int)dtype, (int)op, root), "ReduceTo");
+    }
+    /*! \brief Sum of count kFloat16 / kBFloat16 elements with a float32
+     *  accumulator and one rounding (include/rdc_amd.h RdcAllreduceAcc32: the
+     *  rule), as Allreduce / ReduceScatter / ReduceTo: the same chunks, the
+     *  same result placement, the same untouched bytes.  Any other dtype fails */
+    virtual void AllreduceAcc32(void* sendrecvbuf, uint64_t count, mpi::DataType dtype) {
+        detail::Check(RdcAllreduceAcc32On(handle_, sendrecvbuf, count, (int)dtype), "AllreduceAcc32");
+    }
+    virtual void ReduceScatterAcc32(void* sendrecvbuf, uint64_t count, mpi::DataType dtype) {
+        detail::Check(RdcReduceScatterAcc32On(handle_, sendrecvbuf, count, (int)dtype), "ReduceScatterAcc32");
+    }
+    virtual void ReduceToAcc32(void* sendrecvbuf, uint64_t count, mpi::DataType dtype, int root) {
+        detail::Check(RdcReduceToAcc32On(handle_, sendrecvbuf, count, (int)dtype, root), "ReduceToAcc32");
     }
     /*! \brief in-place prefix reduction across ranks (host or device memory;
      *  MPI_Scan, exclusive: MPI_Exscan): rank r ends with the left fold of
@@ -812,6 +845,41 @@ template <typename OP, typename DType>
 inline void ReduceTo(DType* sendrecvbuf, uint64_t count, int root, const std::string& comm_name = kMainCommName) {
     static_assert(detail::CheckOpType<OP, DType>::value, "");
     GetCommunicator(comm_name)->ReduceTo(sendrecvbuf, count, mpi::GetType<DType>(), OP::kType, root);
+}
+
+/*! \brief in-place Sum of 16-bit floating elements (rdc::Float16 /
+ *  rdc::BFloat16) with a float32 accumulator (MI355X addition; the rule:
+ *  include/rdc_amd.h RdcAllreduceAcc32).  Allreduce<op::Sum> on such elements
+ *  would round to 16 bits at every hop; here the owner of a chunk adds the n
+ *  contributions in binary32, in the ring order, and rounds once.  At two
+ *  ranks the bits are the ordinary Sum's */
+template <typename DType>
+inline void AllreduceAcc32(DType* sendrecvbuf, uint64_t count, const std::string& comm_name = kMainCommName) {
+    if (GetWorldSize() == 1 || count == 0) return;  // as Allreduce
+    GetCommunicator(comm_name)->AllreduceAcc32(sendrecvbuf, count, detail::Acc32Type<DType>::kType);
+}
+
+/*! \brief ReduceScatter's float32-accumulated Sum: returns this rank's element
+ *  range [first, second) of utils::Split(0, count, n), which holds
+ *  AllreduceAcc32's bits on return; every other element stays as passed */
+template <typename DType>
+inline std::pair<uint64_t, uint64_t> ReduceScatterAcc32(DType* sendrecvbuf, uint64_t count,
+                                                        const std::string& comm_name = kMainCommName) {
+    const mpi::DataType dt = detail::Acc32Type<DType>::kType;
+    if (GetWorldSize() == 1 || count == 0) return std::pair<uint64_t, uint64_t>(0, count);
+    comm::ICommunicator* c = GetCommunicator(comm_name);
+    c->ReduceScatterAcc32(sendrecvbuf, count, dt);
+    uint64_t lo = 0, hi = 0;
+    detail::Check(RdcPlanSplit(count, c->GetWorldSize(), c->GetRank(), &lo, &hi), "ReduceScatterAcc32");
+    return std::pair<uint64_t, uint64_t>(lo, hi);
+}
+
+/*! \brief ReduceTo's float32-accumulated Sum: root receives AllreduceAcc32's
+ *  bits, every other rank's buffer stays exactly as passed; a root outside
+ *  [0, GetWorldSize()) fails before anything is launched */
+template <typename DType>
+inline void ReduceToAcc32(DType* sendrecvbuf, uint64_t count, int root, const std::string& comm_name = kMainCommName) {
+    GetCommunicator(comm_name)->ReduceToAcc32(sendrecvbuf, count, detail::Acc32Type<DType>::kType, root);
 }
 
 /*! \brief in-place inclusive prefix reduction across ranks (MI355X addition to

@@ -171,6 +171,44 @@ int RdcReduceScatterOn(void* comm, void* sendrecv, size_t count, int dtype, int 
 int RdcReduceTo(void* sendrecv, size_t count, int dtype, int op, int root);
 int RdcReduceToOn(void* comm, void* sendrecv, size_t count, int dtype, int op, int root);
 
+/* Sum of float16 (dtype 10) / bfloat16 (dtype 11) buffers with a float32
+ * accumulator (MI355X addition).  The ordinary Sum rounds to 16 bits at every
+ * hop (the reference's rule: n - 1 roundings); here the owner of a chunk adds
+ * the n raw contributions in binary32 and rounds ONCE.  THE RULE, for element
+ * e of chunk c = utils::Split(0, count, n)[c], x[q] rank q's value:
+ *     s = f32(x[c-1]);  for j = 2..n:  s = f32(x[c-j]) + s     (indices mod n)
+ *     result = round_to_T(s)
+ * f32() is exact; every add is an IEEE binary32 add, round to nearest even,
+ * subnormals kept; round_to_T is one round-to-nearest-even conversion
+ * (overflow gives inf; a NaN stays a NaN, its payload is not pinned).  The
+ * sequence x[c-1], x[c-2], ..., x[c] is the ring order every schedule folds
+ * in, so each element has one defined bit pattern that tiling and piece cuts
+ * cannot change.  rdc_reduce_ring_mincount is not consulted: there is no tree
+ * branch.  At n = 2 the result is bit-identical to the ordinary Sum (one
+ * binary32 add of two 16-bit values, rounded once, is their correctly rounded
+ * 16-bit sum).  For n > 2 the result is the rounding of the float32 fold,
+ * which is not always the correctly rounded exact sum.
+ * Three collectives, each with its sibling's chunk map, result placement and
+ * untouched bytes: RdcAllreduceAcc32 (every rank receives all count elements),
+ * RdcReduceScatterAcc32 (chunk `rank` receives its elements, every byte
+ * outside it stays exactly as passed), RdcReduceToAcc32 (rank `root` receives
+ * all count elements, every other rank's buffer is only read).  Refused with
+ * a message in RdcGetLastError before anything is launched: a dtype other
+ * than 10 / 11 ("rdc: float32-accumulated Sum needs float16 or bfloat16, got
+ * dtype N"), a root outside [0, n), a buffer not aligned to its element size,
+ * a null buffer with count > 0.  count = 0 or world size 1 succeed without
+ * touching the GPU.  Host or device memory (detected); synchronous.  A host
+ * buffer goes up whole on every rank and comes back where the siblings copy
+ * back: whole (allreduce), chunk `rank` only (reduce-scatter), whole on the
+ * root only (reduce-to: a non-root host buffer is never written).  The calls
+ * without a handle use the "main" communicator. */
+int RdcAllreduceAcc32(void* sendrecv, size_t count, int dtype);
+int RdcAllreduceAcc32On(void* comm, void* sendrecv, size_t count, int dtype);
+int RdcReduceScatterAcc32(void* sendrecv, size_t count, int dtype);
+int RdcReduceScatterAcc32On(void* comm, void* sendrecv, size_t count, int dtype);
+int RdcReduceToAcc32(void* sendrecv, size_t count, int dtype, int root);
+int RdcReduceToAcc32On(void* comm, void* sendrecv, size_t count, int dtype, int root);
+
 /* Prefix reduction across ranks, in place (MPI_Scan; exclusive = 1: MPI_Exscan;
  * MI355X addition: the reference has no scan).  With x[q] rank q's input, y[0]
  * = x[0] and y[q] = OP::Reduce(dst = y[q-1], src = x[q]): a left fold in rank
@@ -375,6 +413,22 @@ int RdcCommAllgather(void* comm, void** dev_bufs, const size_t* sizes, void* str
  * the same bytes.  RdcCommLastLaunch reports algo 2, and gather blocks on the
  * root only. */
 int RdcCommReduceTo(void* comm, void* dev_buf, size_t count, int dtype, int op, int root, void* stream);
+/* Device-resident float32-accumulated Sum of float16 / bfloat16 (see
+ * RdcAllreduceAcc32 for the rule, the results and the refusals),
+ * stream-ordered; errors raised inside the kernels surface at RdcCommCheck.
+ * One schedule each, the pushed mesh (algo 2) at every size and every n, n = 2
+ * included: RdcCommAllreduceEx's mesh, RdcCommReduceScatter's and
+ * RdcCommReduceTo's launches with the owner's fold widened — same bytes, same
+ * hand-offs, same plans (RdcPlanAllreduce algo 2 / RdcPlanReduceScatter /
+ * RdcPlanReduceTo), same launch kinds.  No one-shot, ring, tree, pull or
+ * direct schedule and no resident host service, so a small call pays the
+ * mesh's two hand-offs.  Works in single-process groups and can be captured in
+ * a hipGraph.  RdcCommTune / RDC_NBLOCKS / RDC_TILE_BYTES apply as for a mesh
+ * Sum of the same bytes; RdcCommLastLaunch reports what the mesh sibling
+ * reports. */
+int RdcCommAllreduceAcc32(void* comm, void* dev_buf, size_t count, int dtype, void* stream);
+int RdcCommReduceScatterAcc32(void* comm, void* dev_buf, size_t count, int dtype, void* stream);
+int RdcCommReduceToAcc32(void* comm, void* dev_buf, size_t count, int dtype, int root, void* stream);
 /* Device-resident in-place scan / exscan (see RdcScan for the result and the
  * refusals), stream-ordered; errors raised inside the kernel surface at
  * RdcCommCheck.  One schedule, on the scratch path (k_scan): the ring's reduce

@@ -56,6 +56,15 @@ def _load():
         "RdcCommReduceTo": (i, [vp, vp, sz, i, i, i, vp]),
         "RdcPlanReduceTo": (i, [i, i, i, sz, i, i, sz, sz, i, ctypes.POINTER(u64), i, ctypes.POINTER(ctypes.c_int)]),
         "RdcPlanReduceToBytes": (i, [i, i, i, sz, i, ctypes.POINTER(u64)]),
+        "RdcAllreduceAcc32": (i, [vp, sz, i]),
+        "RdcAllreduceAcc32On": (i, [vp, vp, sz, i]),
+        "RdcCommAllreduceAcc32": (i, [vp, vp, sz, i, vp]),
+        "RdcReduceScatterAcc32": (i, [vp, sz, i]),
+        "RdcReduceScatterAcc32On": (i, [vp, vp, sz, i]),
+        "RdcCommReduceScatterAcc32": (i, [vp, vp, sz, i, vp]),
+        "RdcReduceToAcc32": (i, [vp, sz, i, i]),
+        "RdcReduceToAcc32On": (i, [vp, vp, sz, i, i]),
+        "RdcCommReduceToAcc32": (i, [vp, vp, sz, i, i, vp]),
         "RdcScan": (i, [vp, sz, i, i, i]),
         "RdcScanOn": (i, [vp, vp, sz, i, i, i]),
         "RdcCommScan": (i, [vp, vp, sz, i, i, i, vp]),

@@ -148,7 +148,33 @@ def _torch_dtype_enum(t):
     return device.dtype_enum(t.dtype)
 
 
-def allreduce(data, op, prepare_fun=None, value=None):
+def acc32_requested(accumulate, op, data):
+    """True when ``accumulate="float32"`` selects the float32-accumulated Sum
+    (RdcAllreduceAcc32 and its siblings: the owner of a chunk adds the ranks'
+    16-bit values in binary32, in the ring order, and rounds once — the
+    ordinary Sum rounds at every hop); False for ``None``.  The op must be
+    Op.SUM and the data numpy.float16, torch.float16 or torch.bfloat16:
+    anything else raises ValueError before the library is called."""
+    if accumulate is None:
+        return False
+    if accumulate != "float32":
+        raise ValueError("rdc_amd: accumulate must be None or \"float32\", got %r" % (accumulate,))
+    if int(op) != Op.SUM.value:
+        raise ValueError("rdc_amd: accumulate=\"float32\" goes with Op.SUM only")
+    if isinstance(data, np.ndarray):
+        ok = data.dtype == np.float16
+    elif type(data).__module__.startswith("torch"):
+        import torch
+        ok = data.dtype in (torch.float16, torch.bfloat16)
+    else:
+        ok = False
+    if not ok:
+        raise ValueError("rdc_amd: accumulate=\"float32\" takes numpy.float16, torch.float16 or torch.bfloat16 data, "
+                         "got %s" % (getattr(data, "dtype", type(data)),))
+    return True
+
+
+def allreduce(data, op, prepare_fun=None, value=None, accumulate=None):
     """Allreduce across ranks.
 
     numpy.ndarray: returns the reduced, flattened array (a copy unless ravel
@@ -157,20 +183,27 @@ def allreduce(data, op, prepare_fun=None, value=None):
     ``prepare_fun(data)``, if given, runs before the reduction.
     Op.MAXLOC / Op.MINLOC: a structured array of dtype F32_I32 / I32_I32 /
     F64_I64 / I64_I64, or an int32 / int64 tensor of pairs read as ``value``
-    (Comm.allreduce).
+    (Comm.allreduce).  ``accumulate="float32"`` (Op.SUM on float16 / bfloat16
+    data only): the float32-accumulated Sum (``acc32_requested``).
     """
     op = int(Op(op) if not isinstance(op, Op) else op)
+    acc32 = acc32_requested(accumulate, op, data)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
         if prepare_fun is not None:
             prepare_fun(data)
+        if acc32:
+            return _comm.get_comm("main").allreduce(data, op, accumulate=accumulate)
         return _comm.get_comm("main").allreduce(data, op, value=value)
+    if acc32:
+        return host_allreduce(data, op, prepare_fun, acc32=True)
     return host_allreduce(data, op, prepare_fun)
 
 
-def host_allreduce(data, op, prepare_fun=None, comm=None):
+def host_allreduce(data, op, prepare_fun=None, comm=None, acc32=False):
     """rdc/core.py:172-217 on a host ndarray: RdcAllreduce on "main", or
-    RdcAllreduceOn on the communicator handle ``comm``."""
+    RdcAllreduceOn on the communicator handle ``comm`` (``acc32``:
+    RdcAllreduceAcc32 / RdcAllreduceAcc32On, same copy rule)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
     if not isinstance(data, np.ndarray):
         raise TypeError("allreduce only takes in numpy.ndarray or torch.Tensor")
@@ -182,6 +215,15 @@ def host_allreduce(data, op, prepare_fun=None, comm=None):
         raise TypeError("data type %s not supported" % str(buf.dtype))
     if not buf.flags.c_contiguous:
         buf = np.ascontiguousarray(buf)
+    if acc32:
+        if prepare_fun is not None:
+            prepare_fun(data)
+        ptr = buf.ctypes.data_as(ctypes.c_void_p)
+        if comm is not None:
+            check_call(_LIB.RdcAllreduceAcc32On(comm, ptr, buf.size, DTYPE_ENUM__[buf.dtype]))
+        else:
+            check_call(_LIB.RdcAllreduceAcc32(ptr, buf.size, DTYPE_ENUM__[buf.dtype]))
+        return buf
     if comm is not None:
         if prepare_fun is not None:
             prepare_fun(data)
@@ -205,31 +247,45 @@ def split_range(count, n, rank):
     return lo.value, hi.value
 
 
-def reduce_scatter(data, op, value=None):
+def reduce_scatter(data, op, value=None, accumulate=None):
     """In-place reduce-scatter on the "main" communicator (RdcReduceScatter;
     TryReduceScatterRing, communicator_collective.cc:115-182): chunk
     ``get_rank()`` of ``split_range(data.size, get_world_size(), get_rank())``
     receives the reduction — the bits ``allreduce`` puts there — and every
     other element of ``data`` stays as passed.  A contiguous numpy.ndarray
     (synchronous) or a ROCm torch.Tensor (stream-ordered on torch's current
-    stream); returns the flat view of this rank's chunk."""
+    stream); returns the flat view of this rank's chunk.
+    ``accumulate="float32"``: the float32-accumulated Sum (``acc32_requested``)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
+    acc32 = acc32_requested(accumulate, op, data)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
+        if acc32:
+            return _comm.get_comm("main").reduce_scatter(data, op, accumulate=accumulate)
         return _comm.get_comm("main").reduce_scatter(data, op, value=value)
+    if acc32:
+        return host_reduce_scatter(data, op, acc32=True)
     return host_reduce_scatter(data, op)
 
 
-def host_reduce_scatter(data, op, comm=None):
+def host_reduce_scatter(data, op, comm=None, acc32=False):
     """reduce_scatter of a host ndarray: RdcReduceScatter on "main", or
-    RdcReduceScatterOn on the Comm ``comm``."""
+    RdcReduceScatterOn on the Comm ``comm`` (``acc32``: RdcReduceScatterAcc32 /
+    RdcReduceScatterAcc32On)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
     if not isinstance(data, np.ndarray) or not data.flags.c_contiguous:
         raise TypeError("reduce_scatter takes a contiguous numpy.ndarray or a torch.Tensor")
     if data.dtype not in DTYPE_ENUM__:
         raise TypeError("data type %s not supported" % str(data.dtype))
     ptr = data.ctypes.data_as(ctypes.c_void_p)
-    if comm is not None:
+    if acc32:
+        if comm is not None:
+            check_call(_LIB.RdcReduceScatterAcc32On(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype]))
+            n, r = comm.world_size, comm.rank
+        else:
+            check_call(_LIB.RdcReduceScatterAcc32(ptr, data.size, DTYPE_ENUM__[data.dtype]))
+            n, r = get_world_size(), get_rank()
+    elif comm is not None:
         check_call(_LIB.RdcReduceScatterOn(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], op))
         n, r = comm.world_size, comm.rank
     else:
@@ -303,30 +359,41 @@ def host_all_to_all_v(send, send_counts, recv, recv_counts, send_displs=None, re
     return recv
 
 
-def reduce(data, op, root, value=None):
+def reduce(data, op, root, value=None, accumulate=None):
     """In-place reduction to rank ``root`` on the "main" communicator
     (RdcReduceTo; MPI_Reduce): on ``root`` ``data`` receives the reduction —
     the bits ``allreduce`` puts there by the ring order, at every size — and
     on every other rank ``data`` stays exactly as passed.  ``root`` must be the
     same on every rank.  A contiguous numpy.ndarray (synchronous) or a ROCm
-    torch.Tensor (stream-ordered on torch's current stream); returns ``data``."""
+    torch.Tensor (stream-ordered on torch's current stream); returns ``data``.
+    ``accumulate="float32"``: the float32-accumulated Sum (``acc32_requested``)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
+    acc32 = acc32_requested(accumulate, op, data)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
+        if acc32:
+            return _comm.get_comm("main").reduce(data, op, root, accumulate=accumulate)
         return _comm.get_comm("main").reduce(data, op, root, value=value)
+    if acc32:
+        return host_reduce(data, op, root, acc32=True)
     return host_reduce(data, op, root)
 
 
-def host_reduce(data, op, root, comm=None):
+def host_reduce(data, op, root, comm=None, acc32=False):
     """reduce of a host ndarray: RdcReduceTo on "main", or RdcReduceToOn on the
-    Comm ``comm``."""
+    Comm ``comm`` (``acc32``: RdcReduceToAcc32 / RdcReduceToAcc32On)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
     if not isinstance(data, np.ndarray) or not data.flags.c_contiguous:
         raise TypeError("reduce takes a contiguous numpy.ndarray or a torch.Tensor")
     if data.dtype not in DTYPE_ENUM__:
         raise TypeError("data type %s not supported" % str(data.dtype))
     ptr = data.ctypes.data_as(ctypes.c_void_p)
-    if comm is not None:
+    if acc32:
+        if comm is not None:
+            check_call(_LIB.RdcReduceToAcc32On(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], int(root)))
+        else:
+            check_call(_LIB.RdcReduceToAcc32(ptr, data.size, DTYPE_ENUM__[data.dtype], int(root)))
+    elif comm is not None:
         check_call(_LIB.RdcReduceToOn(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], op, int(root)))
     else:
         check_call(_LIB.RdcReduceTo(ptr, data.size, DTYPE_ENUM__[data.dtype], op, int(root)))

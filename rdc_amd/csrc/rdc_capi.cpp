@@ -445,6 +445,80 @@ void reduce_to_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, i
     c->Check(s);
 }
 
+// ---- float32-accumulated Sum of float16 / bfloat16 (RdcAllreduceAcc32) ----
+void check_acc32_dtype(int dtype) {
+    if (dtype != RDC_DT_FLOAT16 && dtype != RDC_DT_BFLOAT16)
+        throw std::invalid_argument("rdc: float32-accumulated Sum needs float16 or bfloat16, got dtype " +
+                                    std::to_string(dtype));
+}
+
+void check_root(int root, int n) {
+    if (root < 0 || root >= n)
+        throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " + std::to_string(n) +
+                                    ")");
+}
+
+// which == 0: allreduce (a host buffer comes back whole), 1: reduce-scatter
+// (chunk `rank` only), 2: reduction to `root` (whole, on the root only)
+void acc32_sync(Manager& m, Communicator* c, int which, void* sendrecv, size_t count, int dtype, int root) {
+    check_acc32_dtype(dtype);
+    if (which == 2) check_root(root, c->size());
+    const size_t esz = rdc_dtype_size(dtype);
+    if ((uintptr_t)sendrecv % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
+    if (c->size() == 1 || count == 0) return;
+    if (!sendrecv) throw std::invalid_argument("rdc: null buffer");
+    hipStream_t s = manager_stream(m, c->device());
+    auto run = [&](void* d) {
+        if (which == 0) c->AllreduceAcc32(d, count, dtype, s);
+        else if (which == 1) c->ReduceScatterAcc32(d, count, dtype, s);
+        else c->ReduceToAcc32(d, count, dtype, root, s);
+    };
+    if (is_device_pointer(sendrecv)) {
+        run(sendrecv);
+        c->Check(s);
+        return;
+    }
+    // host buffer: the whole input up on every rank, the device collective,
+    // and back exactly the bytes the collective defines on this rank
+    char* d = static_cast<char*>(staging(m, std::max<size_t>(count * esz, 256), c->device()));
+    hcheck(hipMemcpyAsync(d, sendrecv, count * esz, hipMemcpyHostToDevice, s), "H2D");
+    run(d);
+    size_t lo = 0, hi = count * esz;
+    if (which == 1) {
+        int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+        SplitRanges((int64_t)count, c->size(), cb, ce);
+        lo = (size_t)cb[c->rank()] * esz;
+        hi = (size_t)ce[c->rank()] * esz;
+    } else if (which == 2 && c->rank() != root) {
+        hi = 0;  // a non-root host buffer is never written
+    }
+    if (hi > lo)
+        hcheck(hipMemcpyAsync(static_cast<char*>(sendrecv) + lo, d + lo, hi - lo, hipMemcpyDeviceToHost, s), "D2H");
+    c->Check(s);
+}
+
+// the "main" communicator's entry: the checks that need no communicator come
+// first, so that world size 1 refuses what every other size refuses
+int acc32_main(int which, void* sendrecv, size_t count, int dtype, int root) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] {
+        require_init(m);
+        check_acc32_dtype(dtype);
+        if (which == 2) check_root(root, m.world);
+        if ((uintptr_t)sendrecv % rdc_dtype_size(dtype))
+            throw std::invalid_argument("rdc: buffer not aligned to its element size");
+        if (m.world == 1 || count == 0) return;
+        acc32_sync(m, get_comm(m, "main", true), which, sendrecv, count, dtype, root);
+    });
+}
+
+int acc32_on(void* comm, int which, void* sendrecv, size_t count, int dtype, int root) {
+    Manager& m = M();
+    std::lock_guard<std::recursive_mutex> lk(m.mu);
+    return guard([&] { acc32_sync(m, as_comm(comm), which, sendrecv, count, dtype, root); });
+}
+
 // synchronous in-place scan / exscan of host or device memory on communicator c
 void scan_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, int dtype, int op, int exclusive) {
     check_dtype_op(dtype, op);
@@ -800,6 +874,33 @@ int RdcReduceToOn(void* comm, void* sendrecv, size_t count, int dtype, int op, i
 
 int RdcCommReduceTo(void* comm, void* dev_buf, size_t count, int dtype, int op, int root, void* stream) {
     return guard([&] { as_comm(comm)->ReduceTo(dev_buf, count, dtype, op, root, static_cast<hipStream_t>(stream)); });
+}
+
+int RdcAllreduceAcc32(void* sendrecv, size_t count, int dtype) { return acc32_main(0, sendrecv, count, dtype, 0); }
+int RdcAllreduceAcc32On(void* comm, void* sendrecv, size_t count, int dtype) {
+    return acc32_on(comm, 0, sendrecv, count, dtype, 0);
+}
+int RdcReduceScatterAcc32(void* sendrecv, size_t count, int dtype) {
+    return acc32_main(1, sendrecv, count, dtype, 0);
+}
+int RdcReduceScatterAcc32On(void* comm, void* sendrecv, size_t count, int dtype) {
+    return acc32_on(comm, 1, sendrecv, count, dtype, 0);
+}
+int RdcReduceToAcc32(void* sendrecv, size_t count, int dtype, int root) {
+    return acc32_main(2, sendrecv, count, dtype, root);
+}
+int RdcReduceToAcc32On(void* comm, void* sendrecv, size_t count, int dtype, int root) {
+    return acc32_on(comm, 2, sendrecv, count, dtype, root);
+}
+int RdcCommAllreduceAcc32(void* comm, void* dev_buf, size_t count, int dtype, void* stream) {
+    return guard([&] { as_comm(comm)->AllreduceAcc32(dev_buf, count, dtype, static_cast<hipStream_t>(stream)); });
+}
+int RdcCommReduceScatterAcc32(void* comm, void* dev_buf, size_t count, int dtype, void* stream) {
+    return guard([&] { as_comm(comm)->ReduceScatterAcc32(dev_buf, count, dtype, static_cast<hipStream_t>(stream)); });
+}
+int RdcCommReduceToAcc32(void* comm, void* dev_buf, size_t count, int dtype, int root, void* stream) {
+    return guard(
+        [&] { as_comm(comm)->ReduceToAcc32(dev_buf, count, dtype, root, static_cast<hipStream_t>(stream)); });
 }
 
 int RdcScan(void* sendrecv, size_t count, int dtype, int op, int exclusive) {

@@ -243,6 +243,15 @@ public:
     // unsupported (dtype, op), a misaligned or null buffer.  root must be the
     // same on every rank.  n == 1 or count == 0: nothing is launched.
     void ReduceTo(void* buf, size_t count, int dtype, int op, int root, hipStream_t stream);
+    // The float32-accumulated Sum of float16 / bfloat16 buffers (dtype 10 / 11;
+    // the rule: include/rdc_amd.h RdcAllreduceAcc32) as allreduce,
+    // reduce-scatter and rooted reduce: their siblings' checks, chunk map,
+    // launches and untouched bytes, on the pushed mesh at every size and every
+    // n (no one-shot, ring, tree, pull or direct schedule; cfg_.ring_mincount
+    // is not consulted).  Any other dtype is refused before any launch.
+    void AllreduceAcc32(void* buf, size_t count, int dtype, hipStream_t stream);
+    void ReduceScatterAcc32(void* buf, size_t count, int dtype, hipStream_t stream);
+    void ReduceToAcc32(void* buf, size_t count, int dtype, int root, hipStream_t stream);
     // In-place prefix reduction across ranks (MPI_Scan; exclusive = 1:
     // MPI_Exscan), stream-ordered: rank r ends with y[r] (exclusive: r > 0 with
     // y[r-1]), y[0] = x[0], y[q] = OP::Reduce(dst = y[q-1], src = x[q]); rank

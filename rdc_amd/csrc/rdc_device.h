@@ -298,6 +298,51 @@ __device__ __forceinline__ v4u reduce16<RDC_OP_SUM, bf16_t>(v4u d, v4u s) {
     }
     return out;
 }
+// ---- float32-accumulated Sum of float16 / bfloat16 (the rule: include/rdc_amd.h, RdcAllreduceAcc32) ----
+// kOpSumAcc32 is a template tag for the mesh family's fold (mesh_fold_elem /
+// mesh_reduce_range, rdc_kernels_impl.h), not an RDC_OP_* code: no OpF and no
+// reduce16 exist for it, get_kernels never sees it, and only
+// rdc_kernels_acc32.hip instantiates kernels with it.  The owner of a chunk
+// holds all n raw 16-bit contributions before it folds, so it widens each to
+// binary32, adds them in the ring order and rounds ONCE (RNE).
+constexpr int kOpSumAcc32 = 0x100;
+namespace acc32 {
+typedef float f2 __attribute__((ext_vector_type(2)));
+// one element
+template <typename T> __device__ __forceinline__ float widen(T x);
+template <> __device__ __forceinline__ float widen<_Float16>(_Float16 x) { return (float)x; }
+template <> __device__ __forceinline__ float widen<bf16_t>(bf16_t x) { return bf16_to_f32(x.bits); }
+template <typename T> __device__ __forceinline__ T narrow(float s);
+template <> __device__ __forceinline__ _Float16 narrow<_Float16>(float s) { return (_Float16)s; }
+template <> __device__ __forceinline__ bf16_t narrow<bf16_t>(float s) {
+    const __bf16 h = (__bf16)s;  // v_cvt_pk_bf16_f32, as OpF<RDC_OP_SUM>
+    bf16_t r;
+    r.bits = __builtin_bit_cast(uint16_t, h);
+    return r;
+}
+// one dword = two elements: float16 by the hardware conversions
+// (v_cvt_f32_f16 per half, v_cvt_pk_f16_f32 back), bfloat16 by a shift and a
+// mask up and v_cvt_pk_bf16_f32 back; the adds between are v_pk_add_f32
+template <typename T> __device__ __forceinline__ f2 widen2(uint32_t w);
+template <> __device__ __forceinline__ f2 widen2<_Float16>(uint32_t w) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    return __builtin_convertvector(__builtin_bit_cast(h2, w), f2);
+}
+template <> __device__ __forceinline__ f2 widen2<bf16_t>(uint32_t w) {
+    const f2 r = {__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+    return r;
+}
+template <typename T> __device__ __forceinline__ uint32_t narrow2(f2 s);
+template <> __device__ __forceinline__ uint32_t narrow2<_Float16>(f2 s) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(s, h2));
+}
+template <> __device__ __forceinline__ uint32_t narrow2<bf16_t>(f2 s) {
+    typedef __bf16 h2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(s, h2));
+}
+}  // namespace acc32
+
 // bf16 Prod has no such form: OpF<RDC_OP_PROD>::apply converts through __bf16,
 // so the generic loop already rounds in hardware (v_cvt_pk_bf16_f32), and a
 // v_pk_mul_f32 form shaped like the one above measured no faster in k_reduce on

@@ -30,6 +30,10 @@ struct KernelSet {
 
 // false if (dtype, op) is not a valid reference combination
 bool get_kernels(int dtype, int op, KernelSet* ks);
+// the float32-accumulated Sum of float16 / bfloat16 (rdc_kernels_acc32.hip):
+// fills mesh, rscatter, rooted and occupancy, every other member is null;
+// false for any other dtype
+bool get_kernels_acc32(int dtype, KernelSet* ks);
 // resident blocks per CU of k_bcast / k_allgather / k_alltoall
 int occupancy_bcast();
 int occupancy_allgather();

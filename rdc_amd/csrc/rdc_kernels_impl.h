@@ -191,8 +191,15 @@ __device__ __forceinline__ void mesh_fold_elem(const CollArgs& a, char* own, con
     auto val = [&](int q) -> T {
         return q == r ? *reinterpret_cast<const T*>(own + e) : ld_elem_sys<T>(slot0 + q * a.slot_bytes + e);
     };
-    T acc = val((f - 1 + n) % n);
-    for (int k = 2; k <= n; ++k) acc = OpF<OP>::apply(val((f - k + n) % n), acc);
+    T acc;
+    if constexpr (OP == kOpSumAcc32) {  // binary32 accumulator, one rounding (rdc_device.h acc32)
+        float s = acc32::widen<T>(val((f - 1 + n) % n));
+        for (int k = 2; k <= n; ++k) s = acc32::widen<T>(val((f - k + n) % n)) + s;
+        acc = acc32::narrow<T>(s);
+    } else {
+        acc = val((f - 1 + n) % n);
+        for (int k = 2; k <= n; ++k) acc = OpF<OP>::apply(val((f - k + n) % n), acc);
+    }
     if (kOut != kOutPeer) *reinterpret_cast<T*>(own + e) = acc;
     if (kOut == kOutAll)
         for (int p = 0; p < n; ++p)
@@ -265,10 +272,28 @@ __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, 
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (!live[u]) continue;
-            v4u acc = v[u][0];
+            v4u acc;
+            if constexpr (OP == kOpSumAcc32) {
+                // eight binary32 accumulators per vector, the k order of the
+                // ring, one conversion back (rdc_device.h acc32)
+                acc32::f2 s[4];
 #pragma unroll
-            for (int k = 2; k <= NMAX; ++k)
-                if (k <= n) acc = reduce16<OP, T>(v[u][k - 1], acc);
+                for (int d = 0; d < 4; ++d) s[d] = acc32::widen2<T>(v[u][0][d]);
+#pragma unroll
+                for (int k = 2; k <= NMAX; ++k) {
+                    if (k <= n) {
+#pragma unroll
+                        for (int d = 0; d < 4; ++d) s[d] = acc32::widen2<T>(v[u][k - 1][d]) + s[d];
+                    }
+                }
+#pragma unroll
+                for (int d = 0; d < 4; ++d) acc[d] = acc32::narrow2<T>(s[d]);
+            } else {
+                acc = v[u][0];
+#pragma unroll
+                for (int k = 2; k <= NMAX; ++k)
+                    if (k <= n) acc = reduce16<OP, T>(v[u][k - 1], acc);
+            }
             const uint64_t b = head + (i + u * stride) * 16;
             if (kOut != kOutPeer) st16(own + b, acc);
             if (kOut == kOutAll) {
@@ -1601,8 +1626,12 @@ __global__ __launch_bounds__(kBlock) void k_mesh(CollArgs a) {
     const uint64_t t0 = wall_clock64();
     uint64_t seq;
     if (!launch_begin(a, &seq)) {
-        if (a.pull) mesh_pull_body<OP, T, NMAX>(a, seq);
-        else mesh_body<OP, T, NMAX>(a, seq);
+        if constexpr (OP == kOpSumAcc32) {  // pushed mesh only (the pull fold has no acc32 body)
+            mesh_body<OP, T, NMAX>(a, seq);
+        } else {
+            if (a.pull) mesh_pull_body<OP, T, NMAX>(a, seq);
+            else mesh_body<OP, T, NMAX>(a, seq);
+        }
     }
     trace_block(a, t0);
     launch_done(a, seq);
