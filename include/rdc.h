@@ -155,6 +155,13 @@ namespace detail {
 template <typename T> struct Acc32Type;
 template <> struct Acc32Type<Float16> { static const mpi::DataType kType = mpi::kFloat16; };
 template <> struct Acc32Type<BFloat16> { static const mpi::DataType kType = mpi::kBFloat16; };
+/*! \brief the element types Avg takes (float, double, rdc::Float16,
+ *  rdc::BFloat16): anything else (AllreduceAvg<int>) does not compile */
+template <typename T> struct AvgType;
+template <> struct AvgType<float> { static const mpi::DataType kType = mpi::kFloat; };
+template <> struct AvgType<double> { static const mpi::DataType kType = mpi::kDouble; };
+template <> struct AvgType<Float16> { static const mpi::DataType kType = mpi::kFloat16; };
+template <> struct AvgType<BFloat16> { static const mpi::DataType kType = mpi::kBFloat16; };
 template <typename T> struct IsValueIndex : std::false_type {};
 template <typename V> struct IsValueIndex<ValueIndex<V>> : std::true_type {};
 /*! \brief MaxLoc / MinLoc fold ValueIndex<V> and nothing else folds it: a
@@ -502,6 +509,21 @@ public:
     }
     virtual void ReduceToAcc32(void* sendrecvbuf, uint64_t count, mpi::DataType dtype, int root) {
         detail::Check(RdcReduceToAcc32On(handle_, sendrecvbuf, count, (int)dtype, root), "ReduceToAcc32");
+    }
+    /*! \brief the mean across ranks of count kFloat / kDouble / kFloat16 /
+     *  kBFloat16 elements (include/rdc_amd.h RdcAllreduceAvg: the rule — the
+     *  ring-order Sum, in float32 for the 16-bit types, then one division by
+     *  the world size before the single rounding), as Allreduce /
+     *  ReduceScatter / ReduceTo: the same chunks, the same result placement,
+     *  the same untouched bytes.  Any other dtype fails */
+    virtual void AllreduceAvg(void* sendrecvbuf, uint64_t count, mpi::DataType dtype) {
+        detail::Check(RdcAllreduceAvgOn(handle_, sendrecvbuf, count, (int)dtype), "AllreduceAvg");
+    }
+    virtual void ReduceScatterAvg(void* sendrecvbuf, uint64_t count, mpi::DataType dtype) {
+        detail::Check(RdcReduceScatterAvgOn(handle_, sendrecvbuf, count, (int)dtype), "ReduceScatterAvg");
+    }
+    virtual void ReduceToAvg(void* sendrecvbuf, uint64_t count, mpi::DataType dtype, int root) {
+        detail::Check(RdcReduceToAvgOn(handle_, sendrecvbuf, count, (int)dtype, root), "ReduceToAvg");
     }
     /*! \brief in-place prefix reduction across ranks (host or device memory;
      *  MPI_Scan, exclusive: MPI_Exscan): rank r ends with the left fold of
@@ -880,6 +902,43 @@ inline std::pair<uint64_t, uint64_t> ReduceScatterAcc32(DType* sendrecvbuf, uint
 template <typename DType>
 inline void ReduceToAcc32(DType* sendrecvbuf, uint64_t count, int root, const std::string& comm_name = kMainCommName) {
     GetCommunicator(comm_name)->ReduceToAcc32(sendrecvbuf, count, detail::Acc32Type<DType>::kType, root);
+}
+
+/*! \brief in-place mean across ranks of float, double, rdc::Float16 or
+ *  rdc::BFloat16 elements (MI355X addition; the rule: include/rdc_amd.h
+ *  RdcAllreduceAvg).  Allreduce<op::Sum> followed by a division is a second
+ *  pass, rounds 16-bit results twice and cannot undo a float16 sum that
+ *  overflowed; here the owner of a chunk divides its ring-order sum (a
+ *  float32 sum for the 16-bit types) by the world size before it stores.  At
+ *  world size 1 or count 0 the buffer is unchanged */
+template <typename DType>
+inline void AllreduceAvg(DType* sendrecvbuf, uint64_t count, const std::string& comm_name = kMainCommName) {
+    const mpi::DataType dt = detail::AvgType<DType>::kType;
+    if (GetWorldSize() == 1 || count == 0) return;  // as Allreduce
+    GetCommunicator(comm_name)->AllreduceAvg(sendrecvbuf, count, dt);
+}
+
+/*! \brief ReduceScatter's mean: returns this rank's element range [first,
+ *  second) of utils::Split(0, count, n), which holds AllreduceAvg's bits on
+ *  return; every other element stays as passed */
+template <typename DType>
+inline std::pair<uint64_t, uint64_t> ReduceScatterAvg(DType* sendrecvbuf, uint64_t count,
+                                                      const std::string& comm_name = kMainCommName) {
+    const mpi::DataType dt = detail::AvgType<DType>::kType;
+    if (GetWorldSize() == 1 || count == 0) return std::pair<uint64_t, uint64_t>(0, count);
+    comm::ICommunicator* c = GetCommunicator(comm_name);
+    c->ReduceScatterAvg(sendrecvbuf, count, dt);
+    uint64_t lo = 0, hi = 0;
+    detail::Check(RdcPlanSplit(count, c->GetWorldSize(), c->GetRank(), &lo, &hi), "ReduceScatterAvg");
+    return std::pair<uint64_t, uint64_t>(lo, hi);
+}
+
+/*! \brief ReduceTo's mean: root receives AllreduceAvg's bits, every other
+ *  rank's buffer stays exactly as passed; a root outside [0, GetWorldSize())
+ *  fails before anything is launched */
+template <typename DType>
+inline void ReduceToAvg(DType* sendrecvbuf, uint64_t count, int root, const std::string& comm_name = kMainCommName) {
+    GetCommunicator(comm_name)->ReduceToAvg(sendrecvbuf, count, detail::AvgType<DType>::kType, root);
 }
 
 /*! \brief in-place inclusive prefix reduction across ranks (MI355X addition to

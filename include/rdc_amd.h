@@ -209,6 +209,52 @@ int RdcReduceScatterAcc32On(void* comm, void* sendrecv, size_t count, int dtype)
 int RdcReduceToAcc32(void* sendrecv, size_t count, int dtype, int root);
 int RdcReduceToAcc32On(void* comm, void* sendrecv, size_t count, int dtype, int root);
 
+/* Avg: the mean across ranks of float32 (dtype 6), float64 (7), float16 (10)
+ * or bfloat16 (11) buffers (MI355X addition; ReduceOp.AVG / ncclAvg elsewhere).
+ * Every other reduction here leaves a sum, and a caller who wants the mean
+ * divides in a second pass: one more launch, one more trip of the buffer
+ * through memory, a second rounding of 16-bit results, and a float16 sum that
+ * overflowed before the division could save it (four ranks of 40000.0: Sum
+ * and RdcAllreduceAcc32 give inf, the mean is 40000.0).  On the mesh the owner
+ * of a chunk holds all n raw contributions and is the only place a result is
+ * produced, so the division happens there, before the single store.  THE
+ * RULE, for element e of chunk c = utils::Split(0, count, n)[c], x[q] rank q's
+ * value, indices mod n:
+ *   float32 / float64 (T):
+ *     s = x[c-1];  for j = 2..n:  s = x[c-j] + s      in T: the ordinary Sum's
+ *     result = s / T(n)                               ring-order bits, then one
+ *                                                     IEEE division
+ *   float16 / bfloat16 (T):
+ *     s = f32(x[c-1]);  for j = 2..n:  s = f32(x[c-j]) + s   (RdcAllreduceAcc32's fold)
+ *     q = s / float(n)                                       in binary32
+ *     result = round_to_T(q)                                 one rounding, overflow -> inf
+ * Every add and the division are IEEE operations, round to nearest even,
+ * subnormals kept.  It is a DIVISION by n, not a multiplication by a rounded
+ * 1 / n: the two differ in 20 - 55 % of random values at n = 3, 5, 6, 7, 12
+ * (at a power-of-two n they are the same bits).  A 16-bit Avg always
+ * accumulates in float32; there is no per-hop 16-bit Avg.  The ring order
+ * holds at every size: rdc_reduce_ring_mincount is not consulted.  inf / n =
+ * inf, inf - inf gives a NaN; NaN payloads are not pinned.
+ * Three collectives, each with its sibling's chunk map, result placement and
+ * untouched bytes: RdcAllreduceAvg (every rank receives all count elements),
+ * RdcReduceScatterAvg (chunk `rank` receives its elements, every byte outside
+ * it stays exactly as passed), RdcReduceToAvg (rank `root` receives all count
+ * elements, every other rank's buffer is only read).  Refused with a message
+ * in RdcGetLastError before anything is launched: any other dtype — integers
+ * and the pair dtypes — ("rdc: Avg takes float32, float64, float16 or
+ * bfloat16, got dtype N"), a root outside [0, n), a buffer not aligned to its
+ * element size, a null buffer with count > 0.  count = 0 or world size 1
+ * succeed without touching the GPU and leave the buffer unchanged (no
+ * division by 1 is stored).  Host or device memory (detected); synchronous;
+ * a host buffer is staged as for RdcAllreduceAcc32.  The calls without a
+ * handle use the "main" communicator. */
+int RdcAllreduceAvg(void* sendrecv, size_t count, int dtype);
+int RdcAllreduceAvgOn(void* comm, void* sendrecv, size_t count, int dtype);
+int RdcReduceScatterAvg(void* sendrecv, size_t count, int dtype);
+int RdcReduceScatterAvgOn(void* comm, void* sendrecv, size_t count, int dtype);
+int RdcReduceToAvg(void* sendrecv, size_t count, int dtype, int root);
+int RdcReduceToAvgOn(void* comm, void* sendrecv, size_t count, int dtype, int root);
+
 /* Prefix reduction across ranks, in place (MPI_Scan; exclusive = 1: MPI_Exscan;
  * MI355X addition: the reference has no scan).  With x[q] rank q's input, y[0]
  * = x[0] and y[q] = OP::Reduce(dst = y[q-1], src = x[q]): a left fold in rank
@@ -429,6 +475,19 @@ int RdcCommReduceTo(void* comm, void* dev_buf, size_t count, int dtype, int op, 
 int RdcCommAllreduceAcc32(void* comm, void* dev_buf, size_t count, int dtype, void* stream);
 int RdcCommReduceScatterAcc32(void* comm, void* dev_buf, size_t count, int dtype, void* stream);
 int RdcCommReduceToAcc32(void* comm, void* dev_buf, size_t count, int dtype, int root, void* stream);
+/* Device-resident Avg (see RdcAllreduceAvg for the rule, the results and the
+ * refusals), stream-ordered; errors raised inside the kernels surface at
+ * RdcCommCheck.  One schedule each, the pushed mesh (algo 2) at every size and
+ * every n, n = 2 included: the mesh siblings' launches with the owner's fold
+ * followed by the division — same bytes, same hand-offs, same plans, same
+ * launch kinds; the divisor is the communicator's size.  No one-shot, ring,
+ * tree, pull or direct schedule and no resident host service.  Works in
+ * single-process groups and can be captured in a hipGraph.  RdcCommTune /
+ * RDC_NBLOCKS / RDC_TILE_BYTES apply as for a mesh Sum of the same bytes;
+ * RdcCommLastLaunch reports what the mesh sibling reports. */
+int RdcCommAllreduceAvg(void* comm, void* dev_buf, size_t count, int dtype, void* stream);
+int RdcCommReduceScatterAvg(void* comm, void* dev_buf, size_t count, int dtype, void* stream);
+int RdcCommReduceToAvg(void* comm, void* dev_buf, size_t count, int dtype, int root, void* stream);
 /* Device-resident in-place scan / exscan (see RdcScan for the result and the
  * refusals), stream-ordered; errors raised inside the kernel surface at
  * RdcCommCheck.  One schedule, on the scratch path (k_scan): the ring's reduce

@@ -65,6 +65,15 @@ def _load():
         "RdcReduceToAcc32": (i, [vp, sz, i, i]),
         "RdcReduceToAcc32On": (i, [vp, vp, sz, i, i]),
         "RdcCommReduceToAcc32": (i, [vp, vp, sz, i, i, vp]),
+        "RdcAllreduceAvg": (i, [vp, sz, i]),
+        "RdcAllreduceAvgOn": (i, [vp, vp, sz, i]),
+        "RdcCommAllreduceAvg": (i, [vp, vp, sz, i, vp]),
+        "RdcReduceScatterAvg": (i, [vp, sz, i]),
+        "RdcReduceScatterAvgOn": (i, [vp, vp, sz, i]),
+        "RdcCommReduceScatterAvg": (i, [vp, vp, sz, i, vp]),
+        "RdcReduceToAvg": (i, [vp, sz, i, i]),
+        "RdcReduceToAvgOn": (i, [vp, vp, sz, i, i]),
+        "RdcCommReduceToAvg": (i, [vp, vp, sz, i, i, vp]),
         "RdcScan": (i, [vp, sz, i, i, i]),
         "RdcScanOn": (i, [vp, vp, sz, i, i, i]),
         "RdcCommScan": (i, [vp, vp, sz, i, i, i, vp]),

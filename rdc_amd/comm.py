@@ -143,37 +143,42 @@ class Comm(object):
     def alloc_kind(self):
         return _LIB.RdcCommAllocKind(self.handle)
 
-    def _acc32(self, which, tensor, op, algo, stream, value, accumulate, root=0):
+    def _acc32(self, which, tensor, op, algo, stream, value, accumulate, root=0, average=False):
         """``accumulate="float32"`` of allreduce / reduce_scatter / reduce: the
         float32-accumulated Sum (core.acc32_requested: Op.SUM on float16 /
-        bfloat16 data, ValueError otherwise), on the mesh only."""
+        bfloat16 data, ValueError otherwise), on the mesh only.
+        ``average=True``: Avg, the mean across ranks (core.average_requested:
+        Op.SUM on float32 / float64 / float16 / bfloat16 data), the same way."""
         from . import core
-        core.acc32_requested(accumulate, op, tensor)
+        avg = core.average_requested(average, accumulate, op, tensor)
+        acc32 = not avg and core.acc32_requested(accumulate, op, tensor)
         if value is not None:
             raise ValueError("rdc_amd: value= goes with Op.MAXLOC / Op.MINLOC only")
         if algo not in ("auto", "mesh"):
-            raise ValueError("rdc_amd: accumulate=\"float32\" runs on the mesh only, got algo %r" % (algo,))
+            raise ValueError("rdc_amd: %s runs on the mesh only, got algo %r"
+                             % ("average=True" if avg else "accumulate=\"float32\"", algo))
         if not _is_tensor(tensor):
             if which == "allreduce":
-                return core.host_allreduce(tensor, op, comm=self.handle, acc32=True)
+                return core.host_allreduce(tensor, op, comm=self.handle, acc32=acc32, average=avg)
             if which == "reduce_scatter":
-                return core.host_reduce_scatter(tensor, op, comm=self, acc32=True)
-            return core.host_reduce(tensor, op, root, comm=self, acc32=True)
+                return core.host_reduce_scatter(tensor, op, comm=self, acc32=acc32, average=avg)
+            return core.host_reduce(tensor, op, root, comm=self, acc32=acc32, average=avg)
         count, dtype = tensor.numel(), _dev.dtype_enum(tensor.dtype)
         _dev._check_tensor(tensor)
         s = stream if stream is not None else _dev.current_stream_ptr(tensor.device)
         ptr = ctypes.c_void_p(tensor.data_ptr())
+        sfx = "Avg" if avg else "Acc32"
         if which == "allreduce":
-            check_call(_LIB.RdcCommAllreduceAcc32(self.handle, ptr, count, dtype, s))
+            check_call(getattr(_LIB, "RdcCommAllreduce" + sfx)(self.handle, ptr, count, dtype, s))
             return tensor
         if which == "reduce_scatter":
-            check_call(_LIB.RdcCommReduceScatterAcc32(self.handle, ptr, count, dtype, s))
+            check_call(getattr(_LIB, "RdcCommReduceScatter" + sfx)(self.handle, ptr, count, dtype, s))
             lo, hi = core.split_range(count, self.world_size, self.rank)
             return tensor.view(-1)[lo:hi]
-        check_call(_LIB.RdcCommReduceToAcc32(self.handle, ptr, count, dtype, int(root), s))
+        check_call(getattr(_LIB, "RdcCommReduceTo" + sfx)(self.handle, ptr, count, dtype, int(root), s))
         return tensor
 
-    def allreduce(self, tensor, op, algo="auto", stream=None, value=None, accumulate=None):
+    def allreduce(self, tensor, op, algo="auto", stream=None, value=None, accumulate=None, average=False):
         """In-place allreduce of a contiguous ROCm tensor on this
         communicator; returns it.  A numpy array takes rdc.allreduce's host
         path and copy rule (rdc/core.py:196-217) on this communicator
@@ -186,9 +191,13 @@ class Comm(object):
         ``accumulate="float32"`` (Op.SUM on float16 / bfloat16 data; also on
         reduce_scatter and reduce): the float32-accumulated Sum
         (RdcCommAllreduceAcc32) — the ranks' values are added in binary32 and
-        rounded once, where the ordinary Sum rounds at every hop."""
-        if accumulate is not None:
-            return self._acc32("allreduce", tensor, op, algo, stream, value, accumulate)
+        rounded once, where the ordinary Sum rounds at every hop.
+        ``average=True`` (Op.SUM on float32 / float64 / float16 / bfloat16
+        data; also on reduce_scatter and reduce): Avg, the mean across ranks
+        (RdcCommAllreduceAvg) — the owner of a chunk divides its sum by the
+        world size before the single rounding and the single store."""
+        if average or accumulate is not None:
+            return self._acc32("allreduce", tensor, op, algo, stream, value, accumulate, average=average)
         if not _is_tensor(tensor):
             from .core import host_allreduce
             return host_allreduce(tensor, op, comm=self.handle)
@@ -199,7 +208,7 @@ class Comm(object):
                                            dtype, int(op), _ALGOS[algo], s))
         return tensor
 
-    def reduce_scatter(self, tensor, op, algo="auto", stream=None, value=None, accumulate=None):
+    def reduce_scatter(self, tensor, op, algo="auto", stream=None, value=None, accumulate=None, average=False):
         """In-place reduce-scatter of a contiguous ROCm tensor (RdcCommReduceScatter;
         TryReduceScatterRing, communicator_collective.cc:115-182): chunk ``rank``
         of ``split_range(tensor.numel(), world_size, rank)`` receives the
@@ -208,8 +217,8 @@ class Comm(object):
         ``algo``: "auto", "mesh" or "direct".  A contiguous numpy array is
         reduced synchronously (RdcReduceScatterOn), in place likewise."""
         from .core import host_reduce_scatter, split_range
-        if accumulate is not None:
-            return self._acc32("reduce_scatter", tensor, op, algo, stream, value, accumulate)
+        if average or accumulate is not None:
+            return self._acc32("reduce_scatter", tensor, op, algo, stream, value, accumulate, average=average)
         if not _is_tensor(tensor):
             return host_reduce_scatter(tensor, op, comm=self)
         count, dtype = _elem_args(tensor, op, value)
@@ -222,7 +231,7 @@ class Comm(object):
             return tensor.view(-1, 2)[lo:hi]
         return tensor.view(-1)[lo:hi]
 
-    def reduce(self, tensor, op, root, stream=None, value=None, accumulate=None):
+    def reduce(self, tensor, op, root, stream=None, value=None, accumulate=None, average=False):
         """In-place reduction of a contiguous ROCm tensor to rank ``root``
         (RdcCommReduceTo; MPI_Reduce): on ``root`` the tensor receives the
         reduction, with the bits ``allreduce`` puts there by the ring order, at
@@ -231,8 +240,8 @@ class Comm(object):
         numpy array is reduced synchronously (RdcReduceToOn), in place
         likewise; a non-root array is never written."""
         from .core import host_reduce
-        if accumulate is not None:
-            return self._acc32("reduce", tensor, op, "auto", stream, value, accumulate, root)
+        if average or accumulate is not None:
+            return self._acc32("reduce", tensor, op, "auto", stream, value, accumulate, root, average=average)
         if not _is_tensor(tensor):
             return host_reduce(tensor, op, root, comm=self)
         count, dtype = _elem_args(tensor, op, value)

@@ -174,7 +174,42 @@ def acc32_requested(accumulate, op, data):
     return True
 
 
-def allreduce(data, op, prepare_fun=None, value=None, accumulate=None):
+def average_requested(average, accumulate, op, data):
+    """True when ``average=True`` selects Avg, the mean across ranks
+    (RdcAllreduceAvg and its siblings: the owner of a chunk divides its
+    ring-order sum by the world size before it stores — one launch, one
+    rounding, and no float16 overflow that a later division cannot undo);
+    False when ``average`` is false.  The op must be Op.SUM and the data
+    float32, float64 or float16 (numpy or torch) or torch.bfloat16.  16-bit
+    data always accumulate in float32, so ``accumulate`` may be ``None`` or
+    ``"float32"`` there, with the same result; on float32 / float64 data
+    ``accumulate`` stays refused (``acc32_requested``).  Anything else raises
+    ValueError before the library is called."""
+    if not average:
+        return False
+    if int(op) != Op.SUM.value:
+        raise ValueError("rdc_amd: average=True goes with Op.SUM only")
+    if isinstance(data, np.ndarray):
+        ok = data.dtype in (np.float32, np.float64, np.float16)
+    elif type(data).__module__.startswith("torch"):
+        import torch
+        ok = data.dtype in (torch.float32, torch.float64, torch.float16, torch.bfloat16)
+    else:
+        ok = False
+    if not ok:
+        raise ValueError("rdc_amd: average=True takes float32, float64 or float16 data (numpy or torch) or "
+                         "torch.bfloat16, got %s" % (getattr(data, "dtype", type(data)),))
+    if accumulate is not None:
+        acc32_requested(accumulate, op, data)
+    return True
+
+
+def _fold_entry(name, average, acc32, on):
+    """The C entry of a blocking mesh-family fold: Rdc<name>Avg / Rdc<name>Acc32, ...On with a handle."""
+    return getattr(_LIB, "Rdc" + name + ("Avg" if average else "Acc32") + ("On" if on else ""))
+
+
+def allreduce(data, op, prepare_fun=None, value=None, accumulate=None, average=False):
     """Allreduce across ranks.
 
     numpy.ndarray: returns the reduced, flattened array (a copy unless ravel
@@ -185,25 +220,31 @@ def allreduce(data, op, prepare_fun=None, value=None, accumulate=None):
     F64_I64 / I64_I64, or an int32 / int64 tensor of pairs read as ``value``
     (Comm.allreduce).  ``accumulate="float32"`` (Op.SUM on float16 / bfloat16
     data only): the float32-accumulated Sum (``acc32_requested``).
+    ``average=True`` (Op.SUM on floating data): the mean across ranks, divided
+    where the result is produced (``average_requested``).
     """
     op = int(Op(op) if not isinstance(op, Op) else op)
-    acc32 = acc32_requested(accumulate, op, data)
+    avg = average_requested(average, accumulate, op, data)
+    acc32 = not avg and acc32_requested(accumulate, op, data)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
         if prepare_fun is not None:
             prepare_fun(data)
+        if avg:
+            return _comm.get_comm("main").allreduce(data, op, accumulate=accumulate, average=True)
         if acc32:
             return _comm.get_comm("main").allreduce(data, op, accumulate=accumulate)
         return _comm.get_comm("main").allreduce(data, op, value=value)
-    if acc32:
-        return host_allreduce(data, op, prepare_fun, acc32=True)
+    if avg or acc32:
+        return host_allreduce(data, op, prepare_fun, acc32=acc32, average=avg)
     return host_allreduce(data, op, prepare_fun)
 
 
-def host_allreduce(data, op, prepare_fun=None, comm=None, acc32=False):
+def host_allreduce(data, op, prepare_fun=None, comm=None, acc32=False, average=False):
     """rdc/core.py:172-217 on a host ndarray: RdcAllreduce on "main", or
     RdcAllreduceOn on the communicator handle ``comm`` (``acc32``:
-    RdcAllreduceAcc32 / RdcAllreduceAcc32On, same copy rule)."""
+    RdcAllreduceAcc32 / RdcAllreduceAcc32On, ``average``: RdcAllreduceAvg /
+    RdcAllreduceAvgOn, same copy rule)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
     if not isinstance(data, np.ndarray):
         raise TypeError("allreduce only takes in numpy.ndarray or torch.Tensor")
@@ -215,14 +256,14 @@ def host_allreduce(data, op, prepare_fun=None, comm=None, acc32=False):
         raise TypeError("data type %s not supported" % str(buf.dtype))
     if not buf.flags.c_contiguous:
         buf = np.ascontiguousarray(buf)
-    if acc32:
+    if acc32 or average:
         if prepare_fun is not None:
             prepare_fun(data)
         ptr = buf.ctypes.data_as(ctypes.c_void_p)
         if comm is not None:
-            check_call(_LIB.RdcAllreduceAcc32On(comm, ptr, buf.size, DTYPE_ENUM__[buf.dtype]))
+            check_call(_fold_entry("Allreduce", average, acc32, True)(comm, ptr, buf.size, DTYPE_ENUM__[buf.dtype]))
         else:
-            check_call(_LIB.RdcAllreduceAcc32(ptr, buf.size, DTYPE_ENUM__[buf.dtype]))
+            check_call(_fold_entry("Allreduce", average, acc32, False)(ptr, buf.size, DTYPE_ENUM__[buf.dtype]))
         return buf
     if comm is not None:
         if prepare_fun is not None:
@@ -247,7 +288,7 @@ def split_range(count, n, rank):
     return lo.value, hi.value
 
 
-def reduce_scatter(data, op, value=None, accumulate=None):
+def reduce_scatter(data, op, value=None, accumulate=None, average=False):
     """In-place reduce-scatter on the "main" communicator (RdcReduceScatter;
     TryReduceScatterRing, communicator_collective.cc:115-182): chunk
     ``get_rank()`` of ``split_range(data.size, get_world_size(), get_rank())``
@@ -255,35 +296,40 @@ def reduce_scatter(data, op, value=None, accumulate=None):
     other element of ``data`` stays as passed.  A contiguous numpy.ndarray
     (synchronous) or a ROCm torch.Tensor (stream-ordered on torch's current
     stream); returns the flat view of this rank's chunk.
-    ``accumulate="float32"``: the float32-accumulated Sum (``acc32_requested``)."""
+    ``accumulate="float32"``: the float32-accumulated Sum (``acc32_requested``);
+    ``average=True``: the mean across ranks (``average_requested``)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
-    acc32 = acc32_requested(accumulate, op, data)
+    avg = average_requested(average, accumulate, op, data)
+    acc32 = not avg and acc32_requested(accumulate, op, data)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
+        if avg:
+            return _comm.get_comm("main").reduce_scatter(data, op, accumulate=accumulate, average=True)
         if acc32:
             return _comm.get_comm("main").reduce_scatter(data, op, accumulate=accumulate)
         return _comm.get_comm("main").reduce_scatter(data, op, value=value)
-    if acc32:
-        return host_reduce_scatter(data, op, acc32=True)
+    if avg or acc32:
+        return host_reduce_scatter(data, op, acc32=acc32, average=avg)
     return host_reduce_scatter(data, op)
 
 
-def host_reduce_scatter(data, op, comm=None, acc32=False):
+def host_reduce_scatter(data, op, comm=None, acc32=False, average=False):
     """reduce_scatter of a host ndarray: RdcReduceScatter on "main", or
     RdcReduceScatterOn on the Comm ``comm`` (``acc32``: RdcReduceScatterAcc32 /
-    RdcReduceScatterAcc32On)."""
+    RdcReduceScatterAcc32On; ``average``: RdcReduceScatterAvg / RdcReduceScatterAvgOn)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
     if not isinstance(data, np.ndarray) or not data.flags.c_contiguous:
         raise TypeError("reduce_scatter takes a contiguous numpy.ndarray or a torch.Tensor")
     if data.dtype not in DTYPE_ENUM__:
         raise TypeError("data type %s not supported" % str(data.dtype))
     ptr = data.ctypes.data_as(ctypes.c_void_p)
-    if acc32:
+    if acc32 or average:
         if comm is not None:
-            check_call(_LIB.RdcReduceScatterAcc32On(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype]))
+            check_call(_fold_entry("ReduceScatter", average, acc32, True)(comm.handle, ptr, data.size,
+                                                                         DTYPE_ENUM__[data.dtype]))
             n, r = comm.world_size, comm.rank
         else:
-            check_call(_LIB.RdcReduceScatterAcc32(ptr, data.size, DTYPE_ENUM__[data.dtype]))
+            check_call(_fold_entry("ReduceScatter", average, acc32, False)(ptr, data.size, DTYPE_ENUM__[data.dtype]))
             n, r = get_world_size(), get_rank()
     elif comm is not None:
         check_call(_LIB.RdcReduceScatterOn(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], op))
@@ -359,40 +405,47 @@ def host_all_to_all_v(send, send_counts, recv, recv_counts, send_displs=None, re
     return recv
 
 
-def reduce(data, op, root, value=None, accumulate=None):
+def reduce(data, op, root, value=None, accumulate=None, average=False):
     """In-place reduction to rank ``root`` on the "main" communicator
     (RdcReduceTo; MPI_Reduce): on ``root`` ``data`` receives the reduction —
     the bits ``allreduce`` puts there by the ring order, at every size — and
     on every other rank ``data`` stays exactly as passed.  ``root`` must be the
     same on every rank.  A contiguous numpy.ndarray (synchronous) or a ROCm
     torch.Tensor (stream-ordered on torch's current stream); returns ``data``.
-    ``accumulate="float32"``: the float32-accumulated Sum (``acc32_requested``)."""
+    ``accumulate="float32"``: the float32-accumulated Sum (``acc32_requested``);
+    ``average=True``: the mean across ranks (``average_requested``)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
-    acc32 = acc32_requested(accumulate, op, data)
+    avg = average_requested(average, accumulate, op, data)
+    acc32 = not avg and acc32_requested(accumulate, op, data)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
+        if avg:
+            return _comm.get_comm("main").reduce(data, op, root, accumulate=accumulate, average=True)
         if acc32:
             return _comm.get_comm("main").reduce(data, op, root, accumulate=accumulate)
         return _comm.get_comm("main").reduce(data, op, root, value=value)
-    if acc32:
-        return host_reduce(data, op, root, acc32=True)
+    if avg or acc32:
+        return host_reduce(data, op, root, acc32=acc32, average=avg)
     return host_reduce(data, op, root)
 
 
-def host_reduce(data, op, root, comm=None, acc32=False):
+def host_reduce(data, op, root, comm=None, acc32=False, average=False):
     """reduce of a host ndarray: RdcReduceTo on "main", or RdcReduceToOn on the
-    Comm ``comm`` (``acc32``: RdcReduceToAcc32 / RdcReduceToAcc32On)."""
+    Comm ``comm`` (``acc32``: RdcReduceToAcc32 / RdcReduceToAcc32On; ``average``:
+    RdcReduceToAvg / RdcReduceToAvgOn)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
     if not isinstance(data, np.ndarray) or not data.flags.c_contiguous:
         raise TypeError("reduce takes a contiguous numpy.ndarray or a torch.Tensor")
     if data.dtype not in DTYPE_ENUM__:
         raise TypeError("data type %s not supported" % str(data.dtype))
     ptr = data.ctypes.data_as(ctypes.c_void_p)
-    if acc32:
+    if acc32 or average:
         if comm is not None:
-            check_call(_LIB.RdcReduceToAcc32On(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], int(root)))
+            check_call(_fold_entry("ReduceTo", average, acc32, True)(comm.handle, ptr, data.size,
+                                                                    DTYPE_ENUM__[data.dtype], int(root)))
         else:
-            check_call(_LIB.RdcReduceToAcc32(ptr, data.size, DTYPE_ENUM__[data.dtype], int(root)))
+            check_call(_fold_entry("ReduceTo", average, acc32, False)(ptr, data.size, DTYPE_ENUM__[data.dtype],
+                                                                     int(root)))
     elif comm is not None:
         check_call(_LIB.RdcReduceToOn(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], op, int(root)))
     else:

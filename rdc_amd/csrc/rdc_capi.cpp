@@ -445,10 +445,18 @@ void reduce_to_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, i
     c->Check(s);
 }
 
-// ---- float32-accumulated Sum of float16 / bfloat16 (RdcAllreduceAcc32) ----
-void check_acc32_dtype(int dtype) {
-    if (dtype != RDC_DT_FLOAT16 && dtype != RDC_DT_BFLOAT16)
+// ---- float32-accumulated Sum of float16 / bfloat16 (RdcAllreduceAcc32) and
+// Avg of float32 / float64 / float16 / bfloat16 (RdcAllreduceAvg): two folds
+// of the mesh family with one staging rule ----
+enum MeshFold { kFoldAcc32 = 0, kFoldAvg = 1 };
+
+void check_fold_dtype(MeshFold fold, int dtype) {
+    const bool f16 = dtype == RDC_DT_FLOAT16 || dtype == RDC_DT_BFLOAT16;
+    if (fold == kFoldAcc32 && !f16)
         throw std::invalid_argument("rdc: float32-accumulated Sum needs float16 or bfloat16, got dtype " +
+                                    std::to_string(dtype));
+    if (fold == kFoldAvg && !f16 && dtype != RDC_DT_FLOAT32 && dtype != RDC_DT_FLOAT64)
+        throw std::invalid_argument("rdc: Avg takes float32, float64, float16 or bfloat16, got dtype " +
                                     std::to_string(dtype));
 }
 
@@ -460,8 +468,9 @@ void check_root(int root, int n) {
 
 // which == 0: allreduce (a host buffer comes back whole), 1: reduce-scatter
 // (chunk `rank` only), 2: reduction to `root` (whole, on the root only)
-void acc32_sync(Manager& m, Communicator* c, int which, void* sendrecv, size_t count, int dtype, int root) {
-    check_acc32_dtype(dtype);
+void acc32_sync(Manager& m, Communicator* c, MeshFold fold, int which, void* sendrecv, size_t count, int dtype,
+                int root) {
+    check_fold_dtype(fold, dtype);
     if (which == 2) check_root(root, c->size());
     const size_t esz = rdc_dtype_size(dtype);
     if ((uintptr_t)sendrecv % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
@@ -469,6 +478,12 @@ void acc32_sync(Manager& m, Communicator* c, int which, void* sendrecv, size_t c
     if (!sendrecv) throw std::invalid_argument("rdc: null buffer");
     hipStream_t s = manager_stream(m, c->device());
     auto run = [&](void* d) {
+        if (fold == kFoldAvg) {
+            if (which == 0) c->AllreduceAvg(d, count, dtype, s);
+            else if (which == 1) c->ReduceScatterAvg(d, count, dtype, s);
+            else c->ReduceToAvg(d, count, dtype, root, s);
+            return;
+        }
         if (which == 0) c->AllreduceAcc32(d, count, dtype, s);
         else if (which == 1) c->ReduceScatterAcc32(d, count, dtype, s);
         else c->ReduceToAcc32(d, count, dtype, root, s);
@@ -499,24 +514,24 @@ void acc32_sync(Manager& m, Communicator* c, int which, void* sendrecv, size_t c
 
 // the "main" communicator's entry: the checks that need no communicator come
 // first, so that world size 1 refuses what every other size refuses
-int acc32_main(int which, void* sendrecv, size_t count, int dtype, int root) {
+int acc32_main(MeshFold fold, int which, void* sendrecv, size_t count, int dtype, int root) {
     Manager& m = M();
     std::lock_guard<std::recursive_mutex> lk(m.mu);
     return guard([&] {
         require_init(m);
-        check_acc32_dtype(dtype);
+        check_fold_dtype(fold, dtype);
         if (which == 2) check_root(root, m.world);
         if ((uintptr_t)sendrecv % rdc_dtype_size(dtype))
             throw std::invalid_argument("rdc: buffer not aligned to its element size");
         if (m.world == 1 || count == 0) return;
-        acc32_sync(m, get_comm(m, "main", true), which, sendrecv, count, dtype, root);
+        acc32_sync(m, get_comm(m, "main", true), fold, which, sendrecv, count, dtype, root);
     });
 }
 
-int acc32_on(void* comm, int which, void* sendrecv, size_t count, int dtype, int root) {
+int acc32_on(void* comm, MeshFold fold, int which, void* sendrecv, size_t count, int dtype, int root) {
     Manager& m = M();
     std::lock_guard<std::recursive_mutex> lk(m.mu);
-    return guard([&] { acc32_sync(m, as_comm(comm), which, sendrecv, count, dtype, root); });
+    return guard([&] { acc32_sync(m, as_comm(comm), fold, which, sendrecv, count, dtype, root); });
 }
 
 // synchronous in-place scan / exscan of host or device memory on communicator c
@@ -876,21 +891,23 @@ int RdcCommReduceTo(void* comm, void* dev_buf, size_t count, int dtype, int op, 
     return guard([&] { as_comm(comm)->ReduceTo(dev_buf, count, dtype, op, root, static_cast<hipStream_t>(stream)); });
 }
 
-int RdcAllreduceAcc32(void* sendrecv, size_t count, int dtype) { return acc32_main(0, sendrecv, count, dtype, 0); }
+int RdcAllreduceAcc32(void* sendrecv, size_t count, int dtype) {
+    return acc32_main(kFoldAcc32, 0, sendrecv, count, dtype, 0);
+}
 int RdcAllreduceAcc32On(void* comm, void* sendrecv, size_t count, int dtype) {
-    return acc32_on(comm, 0, sendrecv, count, dtype, 0);
+    return acc32_on(comm, kFoldAcc32, 0, sendrecv, count, dtype, 0);
 }
 int RdcReduceScatterAcc32(void* sendrecv, size_t count, int dtype) {
-    return acc32_main(1, sendrecv, count, dtype, 0);
+    return acc32_main(kFoldAcc32, 1, sendrecv, count, dtype, 0);
 }
 int RdcReduceScatterAcc32On(void* comm, void* sendrecv, size_t count, int dtype) {
-    return acc32_on(comm, 1, sendrecv, count, dtype, 0);
+    return acc32_on(comm, kFoldAcc32, 1, sendrecv, count, dtype, 0);
 }
 int RdcReduceToAcc32(void* sendrecv, size_t count, int dtype, int root) {
-    return acc32_main(2, sendrecv, count, dtype, root);
+    return acc32_main(kFoldAcc32, 2, sendrecv, count, dtype, root);
 }
 int RdcReduceToAcc32On(void* comm, void* sendrecv, size_t count, int dtype, int root) {
-    return acc32_on(comm, 2, sendrecv, count, dtype, root);
+    return acc32_on(comm, kFoldAcc32, 2, sendrecv, count, dtype, root);
 }
 int RdcCommAllreduceAcc32(void* comm, void* dev_buf, size_t count, int dtype, void* stream) {
     return guard([&] { as_comm(comm)->AllreduceAcc32(dev_buf, count, dtype, static_cast<hipStream_t>(stream)); });
@@ -901,6 +918,35 @@ int RdcCommReduceScatterAcc32(void* comm, void* dev_buf, size_t count, int dtype
 int RdcCommReduceToAcc32(void* comm, void* dev_buf, size_t count, int dtype, int root, void* stream) {
     return guard(
         [&] { as_comm(comm)->ReduceToAcc32(dev_buf, count, dtype, root, static_cast<hipStream_t>(stream)); });
+}
+
+int RdcAllreduceAvg(void* sendrecv, size_t count, int dtype) {
+    return acc32_main(kFoldAvg, 0, sendrecv, count, dtype, 0);
+}
+int RdcAllreduceAvgOn(void* comm, void* sendrecv, size_t count, int dtype) {
+    return acc32_on(comm, kFoldAvg, 0, sendrecv, count, dtype, 0);
+}
+int RdcReduceScatterAvg(void* sendrecv, size_t count, int dtype) {
+    return acc32_main(kFoldAvg, 1, sendrecv, count, dtype, 0);
+}
+int RdcReduceScatterAvgOn(void* comm, void* sendrecv, size_t count, int dtype) {
+    return acc32_on(comm, kFoldAvg, 1, sendrecv, count, dtype, 0);
+}
+int RdcReduceToAvg(void* sendrecv, size_t count, int dtype, int root) {
+    return acc32_main(kFoldAvg, 2, sendrecv, count, dtype, root);
+}
+int RdcReduceToAvgOn(void* comm, void* sendrecv, size_t count, int dtype, int root) {
+    return acc32_on(comm, kFoldAvg, 2, sendrecv, count, dtype, root);
+}
+int RdcCommAllreduceAvg(void* comm, void* dev_buf, size_t count, int dtype, void* stream) {
+    return guard([&] { as_comm(comm)->AllreduceAvg(dev_buf, count, dtype, static_cast<hipStream_t>(stream)); });
+}
+int RdcCommReduceScatterAvg(void* comm, void* dev_buf, size_t count, int dtype, void* stream) {
+    return guard([&] { as_comm(comm)->ReduceScatterAvg(dev_buf, count, dtype, static_cast<hipStream_t>(stream)); });
+}
+int RdcCommReduceToAvg(void* comm, void* dev_buf, size_t count, int dtype, int root, void* stream) {
+    return guard(
+        [&] { as_comm(comm)->ReduceToAvg(dev_buf, count, dtype, root, static_cast<hipStream_t>(stream)); });
 }
 
 int RdcScan(void* sendrecv, size_t count, int dtype, int op, int exclusive) {

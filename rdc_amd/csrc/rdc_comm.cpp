@@ -1431,6 +1431,79 @@ void Communicator::ReduceToAcc32(void* buf, size_t count, int dtype, int root, h
     LaunchReduceTo(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, root, stream);
 }
 
+// Avg, the mean across ranks (include/rdc_amd.h RdcAllreduceAvg: the ring-order
+// Sum fold, in binary32 for float16 / bfloat16, then one IEEE division by n
+// where the owner of a chunk produces the result), as the three collectives of
+// the mesh family.  Built like the float32-accumulated Sum above: the
+// siblings' checks in their order, the same chunks, the avg KernelSet handed
+// to the siblings' launchers.  The divisor is CollArgs::n; nothing else is new.
+namespace {
+KernelSet avg_kernels(int dtype) {
+    KernelSet ks;
+    if (!get_kernels_avg(dtype, &ks))
+        throw std::invalid_argument("rdc: Avg takes float32, float64, float16 or bfloat16, got dtype " +
+                                    std::to_string(dtype));
+    return ks;
+}
+}  // namespace
+
+void Communicator::AllreduceAvg(void* buf, size_t count, int dtype, hipStream_t stream) {
+    const KernelSet ks = avg_kernels(dtype);
+    const size_t esz = rdc_dtype_size(dtype);
+    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
+    if (n_ == 1 || count == 0) return;
+    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ChannelCall call(ch_.get(), stream);
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
+    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
+    for (int c = 0; c < n_; ++c) {
+        off[c] = (uint64_t)cb[c] * esz;
+        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
+    }
+    LaunchRanges(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, RDC_ALGO_MESH, stream);
+}
+
+void Communicator::ReduceScatterAvg(void* buf, size_t count, int dtype, hipStream_t stream) {
+    const KernelSet ks = avg_kernels(dtype);
+    const size_t esz = rdc_dtype_size(dtype);
+    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
+    if (n_ == 1 || count == 0) return;
+    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ChannelCall call(ch_.get(), stream);
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
+    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
+    for (int c = 0; c < n_; ++c) {
+        off[c] = (uint64_t)cb[c] * esz;
+        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
+    }
+    LaunchReduceScatter(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, stream);
+}
+
+void Communicator::ReduceToAvg(void* buf, size_t count, int dtype, int root, hipStream_t stream) {
+    const KernelSet ks = avg_kernels(dtype);
+    if (root < 0 || root >= n_)
+        throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " + std::to_string(n_) +
+                                    ")");
+    const size_t esz = rdc_dtype_size(dtype);
+    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
+    if (n_ == 1 || count == 0) return;
+    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ChannelCall call(ch_.get(), stream);
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
+    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
+    for (int c = 0; c < n_; ++c) {
+        off[c] = (uint64_t)cb[c] * esz;
+        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
+    }
+    LaunchReduceTo(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, root, stream);
+}
+
 // The prefix reduction across ranks (MPI_Scan / MPI_Exscan), in place: rank r
 // ends with y[r] (inclusive) or, r > 0, y[r-1] (exclusive), where y[0] = x[0]
 // and y[q] = OP::Reduce(dst = y[q-1], src = x[q]) — a left fold in rank order,

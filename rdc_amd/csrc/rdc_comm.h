@@ -252,6 +252,17 @@ public:
     void AllreduceAcc32(void* buf, size_t count, int dtype, hipStream_t stream);
     void ReduceScatterAcc32(void* buf, size_t count, int dtype, hipStream_t stream);
     void ReduceToAcc32(void* buf, size_t count, int dtype, int root, hipStream_t stream);
+    // Avg, the mean across ranks of float32 / float64 / float16 / bfloat16
+    // buffers (dtype 6 / 7 / 10 / 11; the rule: include/rdc_amd.h
+    // RdcAllreduceAvg: the ring-order Sum fold — in binary32 for the 16-bit
+    // types — then one IEEE division by n before the single store) as
+    // allreduce, reduce-scatter and rooted reduce: their siblings' checks,
+    // chunk map, launches and untouched bytes, on the pushed mesh at every
+    // size and every n (cfg_.ring_mincount is not consulted).  Any other dtype
+    // is refused before any launch.
+    void AllreduceAvg(void* buf, size_t count, int dtype, hipStream_t stream);
+    void ReduceScatterAvg(void* buf, size_t count, int dtype, hipStream_t stream);
+    void ReduceToAvg(void* buf, size_t count, int dtype, int root, hipStream_t stream);
     // In-place prefix reduction across ranks (MPI_Scan; exclusive = 1:
     // MPI_Exscan), stream-ordered: rank r ends with y[r] (exclusive: r > 0 with
     // y[r-1]), y[0] = x[0], y[q] = OP::Reduce(dst = y[q-1], src = x[q]); rank

@@ -343,6 +343,35 @@ template <> __device__ __forceinline__ uint32_t narrow2<bf16_t>(f2 s) {
 }
 }  // namespace acc32
 
+// ---- Avg: the mean across ranks (the rule: include/rdc_amd.h, RdcAllreduceAvg) ----
+// kOpAvg is a template tag like kOpSumAcc32, not an RDC_OP_* code: get_kernels
+// never sees it and only rdc_kernels_avg.hip instantiates kernels with it.
+// The owner of a chunk is the only place a result is produced, so it divides
+// there, before the single store.  float / double: the ordinary Sum's ring
+// fold in T, then one IEEE division by T(n).  float16 / bfloat16: the acc32
+// fold, one binary32 division by float(n), one rounding to 16 bits.  A true
+// division (v_div_scale / v_rcp / v_div_fmas / v_div_fixup under
+// -fno-fast-math), never a multiplication by a rounded 1 / n.
+constexpr int kOpAvg = 0x101;
+// the folds that accumulate 16-bit elements in binary32
+template <int OP, typename T>
+constexpr bool kFoldAcc32 = OP == kOpSumAcc32 || (OP == kOpAvg && sizeof(T) == 2);
+namespace avg {
+// the lanes of a 16-byte vector of float (4) / double (2), each divided by T(n)
+template <typename T>
+__device__ __forceinline__ v4u div16(v4u v, int n) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "float or double");
+    constexpr int K = 16 / sizeof(T);
+    const T dn = (T)n;
+    T a[K];
+    __builtin_memcpy(a, &v, 16);
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] = a[k] / dn;
+    __builtin_memcpy(&v, a, 16);
+    return v;
+}
+}  // namespace avg
+
 // bf16 Prod has no such form: OpF<RDC_OP_PROD>::apply converts through __bf16,
 // so the generic loop already rounds in hardware (v_cvt_pk_bf16_f32), and a
 // v_pk_mul_f32 form shaped like the one above measured no faster in k_reduce on

@@ -34,6 +34,10 @@ bool get_kernels(int dtype, int op, KernelSet* ks);
 // fills mesh, rscatter, rooted and occupancy, every other member is null;
 // false for any other dtype
 bool get_kernels_acc32(int dtype, KernelSet* ks);
+// Avg, the mean across ranks of float32 / float64 / float16 / bfloat16
+// (rdc_kernels_avg.hip): fills mesh, rscatter, rooted and occupancy, every
+// other member is null; false for any other dtype
+bool get_kernels_avg(int dtype, KernelSet* ks);
 // resident blocks per CU of k_bcast / k_allgather / k_alltoall
 int occupancy_bcast();
 int occupancy_allgather();

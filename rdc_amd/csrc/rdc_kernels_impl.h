@@ -192,10 +192,15 @@ __device__ __forceinline__ void mesh_fold_elem(const CollArgs& a, char* own, con
         return q == r ? *reinterpret_cast<const T*>(own + e) : ld_elem_sys<T>(slot0 + q * a.slot_bytes + e);
     };
     T acc;
-    if constexpr (OP == kOpSumAcc32) {  // binary32 accumulator, one rounding (rdc_device.h acc32)
+    if constexpr (kFoldAcc32<OP, T>) {  // binary32 accumulator, one rounding (rdc_device.h acc32)
         float s = acc32::widen<T>(val((f - 1 + n) % n));
         for (int k = 2; k <= n; ++k) s = acc32::widen<T>(val((f - k + n) % n)) + s;
+        if constexpr (OP == kOpAvg) s = s / (float)n;  // the mean, before the one rounding
         acc = acc32::narrow<T>(s);
+    } else if constexpr (OP == kOpAvg) {  // float / double: the Sum's fold, one division (rdc_device.h avg)
+        acc = val((f - 1 + n) % n);
+        for (int k = 2; k <= n; ++k) acc = OpF<RDC_OP_SUM>::apply(val((f - k + n) % n), acc);
+        acc = acc / (T)n;
     } else {
         acc = val((f - 1 + n) % n);
         for (int k = 2; k <= n; ++k) acc = OpF<OP>::apply(val((f - k + n) % n), acc);
@@ -273,7 +278,7 @@ __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, 
         for (int u = 0; u < U; ++u) {
             if (!live[u]) continue;
             v4u acc;
-            if constexpr (OP == kOpSumAcc32) {
+            if constexpr (kFoldAcc32<OP, T>) {
                 // eight binary32 accumulators per vector, the k order of the
                 // ring, one conversion back (rdc_device.h acc32)
                 acc32::f2 s[4];
@@ -286,8 +291,21 @@ __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, 
                         for (int d = 0; d < 4; ++d) s[d] = acc32::widen2<T>(v[u][k - 1][d]) + s[d];
                     }
                 }
+                if constexpr (OP == kOpAvg) {  // the mean: a packed division by the wave-uniform float(n)
+                    const float dn = (float)n;
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) s[d] = s[d] / dn;
+                }
 #pragma unroll
                 for (int d = 0; d < 4; ++d) acc[d] = acc32::narrow2<T>(s[d]);
+            } else if constexpr (OP == kOpAvg) {
+                // float / double: the ordinary Sum's chain, then a division of
+                // the vector's 4 / 2 lanes (rdc_device.h avg)
+                acc = v[u][0];
+#pragma unroll
+                for (int k = 2; k <= NMAX; ++k)
+                    if (k <= n) acc = reduce16<RDC_OP_SUM, T>(v[u][k - 1], acc);
+                acc = avg::div16<T>(acc, n);
             } else {
                 acc = v[u][0];
 #pragma unroll
@@ -1626,7 +1644,7 @@ __global__ __launch_bounds__(kBlock) void k_mesh(CollArgs a) {
     const uint64_t t0 = wall_clock64();
     uint64_t seq;
     if (!launch_begin(a, &seq)) {
-        if constexpr (OP == kOpSumAcc32) {  // pushed mesh only (the pull fold has no acc32 body)
+        if constexpr (OP == kOpSumAcc32 || OP == kOpAvg) {  // pushed mesh only (the pull fold has no acc32 / avg body)
             mesh_body<OP, T, NMAX>(a, seq);
         } else {
             if (a.pull) mesh_pull_body<OP, T, NMAX>(a, seq);
