@@ -143,39 +143,37 @@ class Comm(object):
     def alloc_kind(self):
         return _LIB.RdcCommAllocKind(self.handle)
 
-    def _acc32(self, which, tensor, op, algo, stream, value, accumulate, root=0, average=False):
-        """``accumulate="float32"`` of allreduce / reduce_scatter / reduce: the
-        float32-accumulated Sum (core.acc32_requested: Op.SUM on float16 /
-        bfloat16 data, ValueError otherwise), on the mesh only.
-        ``average=True``: Avg, the mean across ranks (core.average_requested:
-        Op.SUM on float32 / float64 / float16 / bfloat16 data), the same way."""
+    def _fold(self, which, tensor, op, algo, stream, value, accumulate, average, root=0):
+        """allreduce / reduce_scatter / reduce under a mesh-family fold
+        (core.fold_requested, ValueError as it raises), on the mesh only:
+        ``accumulate="float32"``, the float32-accumulated Sum (Op.SUM on
+        float16 / bfloat16 data), or ``average=True``, Avg, the mean across
+        ranks (Op.SUM on float32 / float64 / float16 / bfloat16 data)."""
         from . import core
-        avg = core.average_requested(average, accumulate, op, tensor)
-        acc32 = not avg and core.acc32_requested(accumulate, op, tensor)
+        fold = core.fold_requested(accumulate, average, op, tensor)
         if value is not None:
             raise ValueError("rdc_amd: value= goes with Op.MAXLOC / Op.MINLOC only")
         if algo not in ("auto", "mesh"):
             raise ValueError("rdc_amd: %s runs on the mesh only, got algo %r"
-                             % ("average=True" if avg else "accumulate=\"float32\"", algo))
+                             % ("average=True" if fold == "Avg" else "accumulate=\"float32\"", algo))
         if not _is_tensor(tensor):
             if which == "allreduce":
-                return core.host_allreduce(tensor, op, comm=self.handle, acc32=acc32, average=avg)
+                return core.host_allreduce(tensor, op, comm=self.handle, fold=fold)
             if which == "reduce_scatter":
-                return core.host_reduce_scatter(tensor, op, comm=self, acc32=acc32, average=avg)
-            return core.host_reduce(tensor, op, root, comm=self, acc32=acc32, average=avg)
+                return core.host_reduce_scatter(tensor, op, comm=self, fold=fold)
+            return core.host_reduce(tensor, op, root, comm=self, fold=fold)
         count, dtype = tensor.numel(), _dev.dtype_enum(tensor.dtype)
         _dev._check_tensor(tensor)
         s = stream if stream is not None else _dev.current_stream_ptr(tensor.device)
         ptr = ctypes.c_void_p(tensor.data_ptr())
-        sfx = "Avg" if avg else "Acc32"
         if which == "allreduce":
-            check_call(getattr(_LIB, "RdcCommAllreduce" + sfx)(self.handle, ptr, count, dtype, s))
+            check_call(getattr(_LIB, "RdcCommAllreduce" + fold)(self.handle, ptr, count, dtype, s))
             return tensor
         if which == "reduce_scatter":
-            check_call(getattr(_LIB, "RdcCommReduceScatter" + sfx)(self.handle, ptr, count, dtype, s))
+            check_call(getattr(_LIB, "RdcCommReduceScatter" + fold)(self.handle, ptr, count, dtype, s))
             lo, hi = core.split_range(count, self.world_size, self.rank)
             return tensor.view(-1)[lo:hi]
-        check_call(getattr(_LIB, "RdcCommReduceTo" + sfx)(self.handle, ptr, count, dtype, int(root), s))
+        check_call(getattr(_LIB, "RdcCommReduceTo" + fold)(self.handle, ptr, count, dtype, int(root), s))
         return tensor
 
     def allreduce(self, tensor, op, algo="auto", stream=None, value=None, accumulate=None, average=False):
@@ -197,7 +195,7 @@ class Comm(object):
         (RdcCommAllreduceAvg) — the owner of a chunk divides its sum by the
         world size before the single rounding and the single store."""
         if average or accumulate is not None:
-            return self._acc32("allreduce", tensor, op, algo, stream, value, accumulate, average=average)
+            return self._fold("allreduce", tensor, op, algo, stream, value, accumulate, average)
         if not _is_tensor(tensor):
             from .core import host_allreduce
             return host_allreduce(tensor, op, comm=self.handle)
@@ -218,7 +216,7 @@ class Comm(object):
         reduced synchronously (RdcReduceScatterOn), in place likewise."""
         from .core import host_reduce_scatter, split_range
         if average or accumulate is not None:
-            return self._acc32("reduce_scatter", tensor, op, algo, stream, value, accumulate, average=average)
+            return self._fold("reduce_scatter", tensor, op, algo, stream, value, accumulate, average)
         if not _is_tensor(tensor):
             return host_reduce_scatter(tensor, op, comm=self)
         count, dtype = _elem_args(tensor, op, value)
@@ -241,7 +239,7 @@ class Comm(object):
         likewise; a non-root array is never written."""
         from .core import host_reduce
         if average or accumulate is not None:
-            return self._acc32("reduce", tensor, op, "auto", stream, value, accumulate, root, average=average)
+            return self._fold("reduce", tensor, op, "auto", stream, value, accumulate, average, root)
         if not _is_tensor(tensor):
             return host_reduce(tensor, op, root, comm=self)
         count, dtype = _elem_args(tensor, op, value)

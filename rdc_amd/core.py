@@ -204,9 +204,20 @@ def average_requested(average, accumulate, op, data):
     return True
 
 
-def _fold_entry(name, average, acc32, on):
+def fold_requested(accumulate, average, op, data):
+    """The mesh-family fold that ``accumulate=`` / ``average=`` select: ``"Avg"``
+    (``average_requested``), ``"Acc32"`` (``acc32_requested``) or ``None`` for
+    the ordinary reduction; ValueError as those two raise it."""
+    if average_requested(average, accumulate, op, data):
+        return "Avg"
+    if acc32_requested(accumulate, op, data):
+        return "Acc32"
+    return None
+
+
+def _fold_entry(name, fold, on):
     """The C entry of a blocking mesh-family fold: Rdc<name>Avg / Rdc<name>Acc32, ...On with a handle."""
-    return getattr(_LIB, "Rdc" + name + ("Avg" if average else "Acc32") + ("On" if on else ""))
+    return getattr(_LIB, "Rdc" + name + fold + ("On" if on else ""))
 
 
 def allreduce(data, op, prepare_fun=None, value=None, accumulate=None, average=False):
@@ -224,27 +235,21 @@ def allreduce(data, op, prepare_fun=None, value=None, accumulate=None, average=F
     where the result is produced (``average_requested``).
     """
     op = int(Op(op) if not isinstance(op, Op) else op)
-    avg = average_requested(average, accumulate, op, data)
-    acc32 = not avg and acc32_requested(accumulate, op, data)
+    fold = fold_requested(accumulate, average, op, data)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
         if prepare_fun is not None:
             prepare_fun(data)
-        if avg:
-            return _comm.get_comm("main").allreduce(data, op, accumulate=accumulate, average=True)
-        if acc32:
-            return _comm.get_comm("main").allreduce(data, op, accumulate=accumulate)
-        return _comm.get_comm("main").allreduce(data, op, value=value)
-    if avg or acc32:
-        return host_allreduce(data, op, prepare_fun, acc32=acc32, average=avg)
-    return host_allreduce(data, op, prepare_fun)
+        return _comm.get_comm("main").allreduce(data, op, value=None if fold else value, accumulate=accumulate,
+                                                average=average)
+    return host_allreduce(data, op, prepare_fun, fold=fold)
 
 
-def host_allreduce(data, op, prepare_fun=None, comm=None, acc32=False, average=False):
+def host_allreduce(data, op, prepare_fun=None, comm=None, fold=None):
     """rdc/core.py:172-217 on a host ndarray: RdcAllreduce on "main", or
-    RdcAllreduceOn on the communicator handle ``comm`` (``acc32``:
-    RdcAllreduceAcc32 / RdcAllreduceAcc32On, ``average``: RdcAllreduceAvg /
-    RdcAllreduceAvgOn, same copy rule)."""
+    RdcAllreduceOn on the communicator handle ``comm`` (``fold``, a
+    ``fold_requested`` value: RdcAllreduceAcc32 / RdcAllreduceAvg, ...On with
+    ``comm``, same copy rule)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
     if not isinstance(data, np.ndarray):
         raise TypeError("allreduce only takes in numpy.ndarray or torch.Tensor")
@@ -256,14 +261,14 @@ def host_allreduce(data, op, prepare_fun=None, comm=None, acc32=False, average=F
         raise TypeError("data type %s not supported" % str(buf.dtype))
     if not buf.flags.c_contiguous:
         buf = np.ascontiguousarray(buf)
-    if acc32 or average:
+    if fold:
         if prepare_fun is not None:
             prepare_fun(data)
         ptr = buf.ctypes.data_as(ctypes.c_void_p)
         if comm is not None:
-            check_call(_fold_entry("Allreduce", average, acc32, True)(comm, ptr, buf.size, DTYPE_ENUM__[buf.dtype]))
+            check_call(_fold_entry("Allreduce", fold, True)(comm, ptr, buf.size, DTYPE_ENUM__[buf.dtype]))
         else:
-            check_call(_fold_entry("Allreduce", average, acc32, False)(ptr, buf.size, DTYPE_ENUM__[buf.dtype]))
+            check_call(_fold_entry("Allreduce", fold, False)(ptr, buf.size, DTYPE_ENUM__[buf.dtype]))
         return buf
     if comm is not None:
         if prepare_fun is not None:
@@ -299,37 +304,30 @@ def reduce_scatter(data, op, value=None, accumulate=None, average=False):
     ``accumulate="float32"``: the float32-accumulated Sum (``acc32_requested``);
     ``average=True``: the mean across ranks (``average_requested``)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
-    avg = average_requested(average, accumulate, op, data)
-    acc32 = not avg and acc32_requested(accumulate, op, data)
+    fold = fold_requested(accumulate, average, op, data)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
-        if avg:
-            return _comm.get_comm("main").reduce_scatter(data, op, accumulate=accumulate, average=True)
-        if acc32:
-            return _comm.get_comm("main").reduce_scatter(data, op, accumulate=accumulate)
-        return _comm.get_comm("main").reduce_scatter(data, op, value=value)
-    if avg or acc32:
-        return host_reduce_scatter(data, op, acc32=acc32, average=avg)
-    return host_reduce_scatter(data, op)
+        return _comm.get_comm("main").reduce_scatter(data, op, value=None if fold else value,
+                                                     accumulate=accumulate, average=average)
+    return host_reduce_scatter(data, op, fold=fold)
 
 
-def host_reduce_scatter(data, op, comm=None, acc32=False, average=False):
+def host_reduce_scatter(data, op, comm=None, fold=None):
     """reduce_scatter of a host ndarray: RdcReduceScatter on "main", or
-    RdcReduceScatterOn on the Comm ``comm`` (``acc32``: RdcReduceScatterAcc32 /
-    RdcReduceScatterAcc32On; ``average``: RdcReduceScatterAvg / RdcReduceScatterAvgOn)."""
+    RdcReduceScatterOn on the Comm ``comm`` (``fold``, a ``fold_requested``
+    value: RdcReduceScatterAcc32 / RdcReduceScatterAvg, ...On with ``comm``)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
     if not isinstance(data, np.ndarray) or not data.flags.c_contiguous:
         raise TypeError("reduce_scatter takes a contiguous numpy.ndarray or a torch.Tensor")
     if data.dtype not in DTYPE_ENUM__:
         raise TypeError("data type %s not supported" % str(data.dtype))
     ptr = data.ctypes.data_as(ctypes.c_void_p)
-    if acc32 or average:
+    if fold:
         if comm is not None:
-            check_call(_fold_entry("ReduceScatter", average, acc32, True)(comm.handle, ptr, data.size,
-                                                                         DTYPE_ENUM__[data.dtype]))
+            check_call(_fold_entry("ReduceScatter", fold, True)(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype]))
             n, r = comm.world_size, comm.rank
         else:
-            check_call(_fold_entry("ReduceScatter", average, acc32, False)(ptr, data.size, DTYPE_ENUM__[data.dtype]))
+            check_call(_fold_entry("ReduceScatter", fold, False)(ptr, data.size, DTYPE_ENUM__[data.dtype]))
             n, r = get_world_size(), get_rank()
     elif comm is not None:
         check_call(_LIB.RdcReduceScatterOn(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], op))
@@ -415,23 +413,17 @@ def reduce(data, op, root, value=None, accumulate=None, average=False):
     ``accumulate="float32"``: the float32-accumulated Sum (``acc32_requested``);
     ``average=True``: the mean across ranks (``average_requested``)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
-    avg = average_requested(average, accumulate, op, data)
-    acc32 = not avg and acc32_requested(accumulate, op, data)
+    fold = fold_requested(accumulate, average, op, data)
     if type(data).__module__.startswith("torch"):
         from . import comm as _comm
-        if avg:
-            return _comm.get_comm("main").reduce(data, op, root, accumulate=accumulate, average=True)
-        if acc32:
-            return _comm.get_comm("main").reduce(data, op, root, accumulate=accumulate)
-        return _comm.get_comm("main").reduce(data, op, root, value=value)
-    if avg or acc32:
-        return host_reduce(data, op, root, acc32=acc32, average=avg)
-    return host_reduce(data, op, root)
+        return _comm.get_comm("main").reduce(data, op, root, value=None if fold else value, accumulate=accumulate,
+                                             average=average)
+    return host_reduce(data, op, root, fold=fold)
 
 
-def host_reduce(data, op, root, comm=None, acc32=False, average=False):
+def host_reduce(data, op, root, comm=None, fold=None):
     """reduce of a host ndarray: RdcReduceTo on "main", or RdcReduceToOn on the
-    Comm ``comm`` (``acc32``: RdcReduceToAcc32 / RdcReduceToAcc32On; ``average``:
+    Comm ``comm`` (``fold``, a ``fold_requested`` value: RdcReduceToAcc32 /
     RdcReduceToAvg / RdcReduceToAvgOn)."""
     op = int(Op(op) if not isinstance(op, Op) else op)
     if not isinstance(data, np.ndarray) or not data.flags.c_contiguous:
@@ -439,13 +431,12 @@ def host_reduce(data, op, root, comm=None, acc32=False, average=False):
     if data.dtype not in DTYPE_ENUM__:
         raise TypeError("data type %s not supported" % str(data.dtype))
     ptr = data.ctypes.data_as(ctypes.c_void_p)
-    if acc32 or average:
+    if fold:
         if comm is not None:
-            check_call(_fold_entry("ReduceTo", average, acc32, True)(comm.handle, ptr, data.size,
-                                                                    DTYPE_ENUM__[data.dtype], int(root)))
+            check_call(_fold_entry("ReduceTo", fold, True)(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype],
+                                                           int(root)))
         else:
-            check_call(_fold_entry("ReduceTo", average, acc32, False)(ptr, data.size, DTYPE_ENUM__[data.dtype],
-                                                                     int(root)))
+            check_call(_fold_entry("ReduceTo", fold, False)(ptr, data.size, DTYPE_ENUM__[data.dtype], int(root)))
     elif comm is not None:
         check_call(_LIB.RdcReduceToOn(comm.handle, ptr, data.size, DTYPE_ENUM__[data.dtype], op, int(root)))
     else:

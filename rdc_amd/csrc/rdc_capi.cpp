@@ -412,9 +412,9 @@ void reduce_scatter_sync(Manager& m, Communicator* c, void* sendrecv, size_t cou
     char* d = static_cast<char*>(staging(m, std::max<size_t>(count * esz, 256), c->device()));
     hcheck(hipMemcpyAsync(d, sendrecv, count * esz, hipMemcpyHostToDevice, s), "H2D");
     c->ReduceScatter(d, count, dtype, op, s);
-    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-    SplitRanges((int64_t)count, c->size(), cb, ce);
-    const size_t lo = (size_t)cb[c->rank()] * esz, hi = (size_t)ce[c->rank()] * esz;
+    uint64_t off[RDC_MAX_RANKS], len[RDC_MAX_RANKS];
+    SplitBytes(count, esz, c->size(), off, len);
+    const size_t lo = off[c->rank()], hi = lo + len[c->rank()];
     if (hi > lo)
         hcheck(hipMemcpyAsync(static_cast<char*>(sendrecv) + lo, d + lo, hi - lo, hipMemcpyDeviceToHost, s), "D2H");
     c->Check(s);
@@ -423,9 +423,7 @@ void reduce_scatter_sync(Manager& m, Communicator* c, void* sendrecv, size_t cou
 // synchronous in-place reduction to `root` of host or device memory on communicator c
 void reduce_to_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, int dtype, int op, int root) {
     check_dtype_op(dtype, op);
-    if (root < 0 || root >= c->size())
-        throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " +
-                                    std::to_string(c->size()) + ")");
+    CheckRoot(root, c->size());
     if (c->size() == 1 || count == 0) return;
     if (!sendrecv) throw std::invalid_argument("rdc: null buffer");
     hipStream_t s = manager_stream(m, c->device());
@@ -447,49 +445,20 @@ void reduce_to_sync(Manager& m, Communicator* c, void* sendrecv, size_t count, i
 
 // ---- float32-accumulated Sum of float16 / bfloat16 (RdcAllreduceAcc32) and
 // Avg of float32 / float64 / float16 / bfloat16 (RdcAllreduceAvg): two folds
-// of the mesh family with one staging rule ----
-enum MeshFold { kFoldAcc32 = 0, kFoldAvg = 1 };
-
-void check_fold_dtype(MeshFold fold, int dtype) {
-    const bool f16 = dtype == RDC_DT_FLOAT16 || dtype == RDC_DT_BFLOAT16;
-    if (fold == kFoldAcc32 && !f16)
-        throw std::invalid_argument("rdc: float32-accumulated Sum needs float16 or bfloat16, got dtype " +
-                                    std::to_string(dtype));
-    if (fold == kFoldAvg && !f16 && dtype != RDC_DT_FLOAT32 && dtype != RDC_DT_FLOAT64)
-        throw std::invalid_argument("rdc: Avg takes float32, float64, float16 or bfloat16, got dtype " +
-                                    std::to_string(dtype));
-}
-
-void check_root(int root, int n) {
-    if (root < 0 || root >= n)
-        throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " + std::to_string(n) +
-                                    ")");
-}
-
-// which == 0: allreduce (a host buffer comes back whole), 1: reduce-scatter
-// (chunk `rank` only), 2: reduction to `root` (whole, on the root only)
-void acc32_sync(Manager& m, Communicator* c, MeshFold fold, int which, void* sendrecv, size_t count, int dtype,
-                int root) {
-    check_fold_dtype(fold, dtype);
-    if (which == 2) check_root(root, c->size());
+// of the mesh family with one staging rule.  An allreduce's host buffer comes
+// back whole, a reduce-scatter's chunk `rank` only, a reduction to `root`
+// whole on the root only ----
+void fold_sync(Manager& m, Communicator* c, MeshFold fold, MeshColl which, void* sendrecv, size_t count, int dtype,
+               int root) {
+    (void)FoldKernels(fold, dtype);
+    if (which == MeshColl::kReduceTo) CheckRoot(root, c->size());
     const size_t esz = rdc_dtype_size(dtype);
     if ((uintptr_t)sendrecv % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
     if (c->size() == 1 || count == 0) return;
     if (!sendrecv) throw std::invalid_argument("rdc: null buffer");
     hipStream_t s = manager_stream(m, c->device());
-    auto run = [&](void* d) {
-        if (fold == kFoldAvg) {
-            if (which == 0) c->AllreduceAvg(d, count, dtype, s);
-            else if (which == 1) c->ReduceScatterAvg(d, count, dtype, s);
-            else c->ReduceToAvg(d, count, dtype, root, s);
-            return;
-        }
-        if (which == 0) c->AllreduceAcc32(d, count, dtype, s);
-        else if (which == 1) c->ReduceScatterAcc32(d, count, dtype, s);
-        else c->ReduceToAcc32(d, count, dtype, root, s);
-    };
     if (is_device_pointer(sendrecv)) {
-        run(sendrecv);
+        c->FoldCollective(which, fold, sendrecv, count, dtype, root, s);
         c->Check(s);
         return;
     }
@@ -497,14 +466,14 @@ void acc32_sync(Manager& m, Communicator* c, MeshFold fold, int which, void* sen
     // and back exactly the bytes the collective defines on this rank
     char* d = static_cast<char*>(staging(m, std::max<size_t>(count * esz, 256), c->device()));
     hcheck(hipMemcpyAsync(d, sendrecv, count * esz, hipMemcpyHostToDevice, s), "H2D");
-    run(d);
+    c->FoldCollective(which, fold, d, count, dtype, root, s);
     size_t lo = 0, hi = count * esz;
-    if (which == 1) {
-        int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-        SplitRanges((int64_t)count, c->size(), cb, ce);
-        lo = (size_t)cb[c->rank()] * esz;
-        hi = (size_t)ce[c->rank()] * esz;
-    } else if (which == 2 && c->rank() != root) {
+    if (which == MeshColl::kReduceScatter) {
+        uint64_t off[RDC_MAX_RANKS], len[RDC_MAX_RANKS];
+        SplitBytes(count, esz, c->size(), off, len);
+        lo = off[c->rank()];
+        hi = lo + len[c->rank()];
+    } else if (which == MeshColl::kReduceTo && c->rank() != root) {
         hi = 0;  // a non-root host buffer is never written
     }
     if (hi > lo)
@@ -514,24 +483,32 @@ void acc32_sync(Manager& m, Communicator* c, MeshFold fold, int which, void* sen
 
 // the "main" communicator's entry: the checks that need no communicator come
 // first, so that world size 1 refuses what every other size refuses
-int acc32_main(MeshFold fold, int which, void* sendrecv, size_t count, int dtype, int root) {
+int fold_main(MeshFold fold, MeshColl which, void* sendrecv, size_t count, int dtype, int root) {
     Manager& m = M();
     std::lock_guard<std::recursive_mutex> lk(m.mu);
     return guard([&] {
         require_init(m);
-        check_fold_dtype(fold, dtype);
-        if (which == 2) check_root(root, m.world);
+        (void)FoldKernels(fold, dtype);
+        if (which == MeshColl::kReduceTo) CheckRoot(root, m.world);
         if ((uintptr_t)sendrecv % rdc_dtype_size(dtype))
             throw std::invalid_argument("rdc: buffer not aligned to its element size");
         if (m.world == 1 || count == 0) return;
-        acc32_sync(m, get_comm(m, "main", true), fold, which, sendrecv, count, dtype, root);
+        fold_sync(m, get_comm(m, "main", true), fold, which, sendrecv, count, dtype, root);
     });
 }
 
-int acc32_on(void* comm, MeshFold fold, int which, void* sendrecv, size_t count, int dtype, int root) {
+int fold_on(void* comm, MeshFold fold, MeshColl which, void* sendrecv, size_t count, int dtype, int root) {
     Manager& m = M();
     std::lock_guard<std::recursive_mutex> lk(m.mu);
-    return guard([&] { acc32_sync(m, as_comm(comm), fold, which, sendrecv, count, dtype, root); });
+    return guard([&] { fold_sync(m, as_comm(comm), fold, which, sendrecv, count, dtype, root); });
+}
+
+// the device-buffer entry on the caller's stream
+int fold_comm(void* comm, MeshFold fold, MeshColl which, void* dev_buf, size_t count, int dtype, int root,
+              void* stream) {
+    return guard([&] {
+        as_comm(comm)->FoldCollective(which, fold, dev_buf, count, dtype, root, static_cast<hipStream_t>(stream));
+    });
 }
 
 // synchronous in-place scan / exscan of host or device memory on communicator c
@@ -892,61 +869,59 @@ int RdcCommReduceTo(void* comm, void* dev_buf, size_t count, int dtype, int op, 
 }
 
 int RdcAllreduceAcc32(void* sendrecv, size_t count, int dtype) {
-    return acc32_main(kFoldAcc32, 0, sendrecv, count, dtype, 0);
+    return fold_main(MeshFold::kAcc32, MeshColl::kAllreduce, sendrecv, count, dtype, 0);
 }
 int RdcAllreduceAcc32On(void* comm, void* sendrecv, size_t count, int dtype) {
-    return acc32_on(comm, kFoldAcc32, 0, sendrecv, count, dtype, 0);
+    return fold_on(comm, MeshFold::kAcc32, MeshColl::kAllreduce, sendrecv, count, dtype, 0);
 }
 int RdcReduceScatterAcc32(void* sendrecv, size_t count, int dtype) {
-    return acc32_main(kFoldAcc32, 1, sendrecv, count, dtype, 0);
+    return fold_main(MeshFold::kAcc32, MeshColl::kReduceScatter, sendrecv, count, dtype, 0);
 }
 int RdcReduceScatterAcc32On(void* comm, void* sendrecv, size_t count, int dtype) {
-    return acc32_on(comm, kFoldAcc32, 1, sendrecv, count, dtype, 0);
+    return fold_on(comm, MeshFold::kAcc32, MeshColl::kReduceScatter, sendrecv, count, dtype, 0);
 }
 int RdcReduceToAcc32(void* sendrecv, size_t count, int dtype, int root) {
-    return acc32_main(kFoldAcc32, 2, sendrecv, count, dtype, root);
+    return fold_main(MeshFold::kAcc32, MeshColl::kReduceTo, sendrecv, count, dtype, root);
 }
 int RdcReduceToAcc32On(void* comm, void* sendrecv, size_t count, int dtype, int root) {
-    return acc32_on(comm, kFoldAcc32, 2, sendrecv, count, dtype, root);
+    return fold_on(comm, MeshFold::kAcc32, MeshColl::kReduceTo, sendrecv, count, dtype, root);
 }
 int RdcCommAllreduceAcc32(void* comm, void* dev_buf, size_t count, int dtype, void* stream) {
-    return guard([&] { as_comm(comm)->AllreduceAcc32(dev_buf, count, dtype, static_cast<hipStream_t>(stream)); });
+    return fold_comm(comm, MeshFold::kAcc32, MeshColl::kAllreduce, dev_buf, count, dtype, 0, stream);
 }
 int RdcCommReduceScatterAcc32(void* comm, void* dev_buf, size_t count, int dtype, void* stream) {
-    return guard([&] { as_comm(comm)->ReduceScatterAcc32(dev_buf, count, dtype, static_cast<hipStream_t>(stream)); });
+    return fold_comm(comm, MeshFold::kAcc32, MeshColl::kReduceScatter, dev_buf, count, dtype, 0, stream);
 }
 int RdcCommReduceToAcc32(void* comm, void* dev_buf, size_t count, int dtype, int root, void* stream) {
-    return guard(
-        [&] { as_comm(comm)->ReduceToAcc32(dev_buf, count, dtype, root, static_cast<hipStream_t>(stream)); });
+    return fold_comm(comm, MeshFold::kAcc32, MeshColl::kReduceTo, dev_buf, count, dtype, root, stream);
 }
 
 int RdcAllreduceAvg(void* sendrecv, size_t count, int dtype) {
-    return acc32_main(kFoldAvg, 0, sendrecv, count, dtype, 0);
+    return fold_main(MeshFold::kAvg, MeshColl::kAllreduce, sendrecv, count, dtype, 0);
 }
 int RdcAllreduceAvgOn(void* comm, void* sendrecv, size_t count, int dtype) {
-    return acc32_on(comm, kFoldAvg, 0, sendrecv, count, dtype, 0);
+    return fold_on(comm, MeshFold::kAvg, MeshColl::kAllreduce, sendrecv, count, dtype, 0);
 }
 int RdcReduceScatterAvg(void* sendrecv, size_t count, int dtype) {
-    return acc32_main(kFoldAvg, 1, sendrecv, count, dtype, 0);
+    return fold_main(MeshFold::kAvg, MeshColl::kReduceScatter, sendrecv, count, dtype, 0);
 }
 int RdcReduceScatterAvgOn(void* comm, void* sendrecv, size_t count, int dtype) {
-    return acc32_on(comm, kFoldAvg, 1, sendrecv, count, dtype, 0);
+    return fold_on(comm, MeshFold::kAvg, MeshColl::kReduceScatter, sendrecv, count, dtype, 0);
 }
 int RdcReduceToAvg(void* sendrecv, size_t count, int dtype, int root) {
-    return acc32_main(kFoldAvg, 2, sendrecv, count, dtype, root);
+    return fold_main(MeshFold::kAvg, MeshColl::kReduceTo, sendrecv, count, dtype, root);
 }
 int RdcReduceToAvgOn(void* comm, void* sendrecv, size_t count, int dtype, int root) {
-    return acc32_on(comm, kFoldAvg, 2, sendrecv, count, dtype, root);
+    return fold_on(comm, MeshFold::kAvg, MeshColl::kReduceTo, sendrecv, count, dtype, root);
 }
 int RdcCommAllreduceAvg(void* comm, void* dev_buf, size_t count, int dtype, void* stream) {
-    return guard([&] { as_comm(comm)->AllreduceAvg(dev_buf, count, dtype, static_cast<hipStream_t>(stream)); });
+    return fold_comm(comm, MeshFold::kAvg, MeshColl::kAllreduce, dev_buf, count, dtype, 0, stream);
 }
 int RdcCommReduceScatterAvg(void* comm, void* dev_buf, size_t count, int dtype, void* stream) {
-    return guard([&] { as_comm(comm)->ReduceScatterAvg(dev_buf, count, dtype, static_cast<hipStream_t>(stream)); });
+    return fold_comm(comm, MeshFold::kAvg, MeshColl::kReduceScatter, dev_buf, count, dtype, 0, stream);
 }
 int RdcCommReduceToAvg(void* comm, void* dev_buf, size_t count, int dtype, int root, void* stream) {
-    return guard(
-        [&] { as_comm(comm)->ReduceToAvg(dev_buf, count, dtype, root, static_cast<hipStream_t>(stream)); });
+    return fold_comm(comm, MeshFold::kAvg, MeshColl::kReduceTo, dev_buf, count, dtype, root, stream);
 }
 
 int RdcScan(void* sendrecv, size_t count, int dtype, int op, int exclusive) {

@@ -1251,16 +1251,47 @@ int Communicator::LaunchGrid(int want, int blocks_per_cu) const {
     return ResidentGrid(want, blocks_per_cu, cus_min_, share_max_, xcds_max_, svc ? share_max_ : 0);
 }
 
-void Communicator::Allreduce(void* buf, size_t count, int dtype, int op, hipStream_t stream, int algo) {
+namespace {
+KernelSet OpKernels(int dtype, int op) {
     KernelSet ks;
     if (!get_kernels(dtype, op, &ks))
         throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
                                     std::to_string(op) + ")");
-    const size_t esz = rdc_dtype_size(dtype);
+    return ks;
+}
+}  // namespace
+
+void CheckRoot(int root, int n) {
+    if (root < 0 || root >= n)
+        throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " + std::to_string(n) +
+                                    ")");
+}
+
+void SplitBytes(size_t count, size_t esz, int n, uint64_t* off, uint64_t* len) {
+    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
+    SplitRanges((int64_t)count, n, cb, ce);
+    for (int c = 0; c < RDC_MAX_RANKS; ++c) off[c] = len[c] = 0;
+    for (int c = 0; c < n; ++c) {
+        off[c] = (uint64_t)cb[c] * esz;
+        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
+    }
+}
+
+// The buffer checks of the in-place collectives, in the order their callers
+// rely on: a misaligned buffer is refused at every world size; world size 1
+// (Communicator::Allreduce returns there, communicator_base.h:133-138) and
+// count 0 launch nothing (false); then a null buffer is refused.
+bool Communicator::HasWork(const void* buf, size_t count, size_t esz) const {
     if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
-    // Communicator::Allreduce returns at world size 1 (communicator_base.h:133-138)
-    if (n_ == 1 || count == 0) return;
+    if (n_ == 1 || count == 0) return false;
     if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    return true;
+}
+
+void Communicator::Allreduce(void* buf, size_t count, int dtype, int op, hipStream_t stream, int algo) {
+    const KernelSet ks = OpKernels(dtype, op);
+    const size_t esz = rdc_dtype_size(dtype);
+    if (!HasWork(buf, count, esz)) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ChannelCall call(ch_.get(), stream);
     // TryAllreduce (communicator_collective.cc:6-13): the ring for buffers of
@@ -1275,13 +1306,8 @@ void Communicator::Allreduce(void* buf, size_t count, int dtype, int op, hipStre
         if (AllreduceDirect(ks, &b0, &nb, 1, esz, stream)) return;
     }
     if (algo == RDC_ALGO_DIRECT) algo = RDC_ALGO_AUTO;  // not registrable here: the scratch schedules
-    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
-    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
-    for (int c = 0; c < n_; ++c) {
-        off[c] = (uint64_t)cb[c] * esz;
-        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
-    }
+    uint64_t off[RDC_MAX_RANKS], len[RDC_MAX_RANKS];
+    SplitBytes(count, esz, n_, off, len);
     LaunchRanges(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, algo, stream);
 }
 
@@ -1298,17 +1324,12 @@ void Communicator::Allreduce(void* buf, size_t count, int dtype, int op, hipStre
 // mesh on every rank.  DirectAuto's 16 / 32 MiB threshold was measured for
 // the allreduce and is PROVISIONAL here (DESIGN.md §7.4 records the sweep).
 void Communicator::ReduceScatter(void* buf, size_t count, int dtype, int op, hipStream_t stream, int algo) {
-    KernelSet ks;
-    if (!get_kernels(dtype, op, &ks))
-        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
-                                    std::to_string(op) + ")");
+    const KernelSet ks = OpKernels(dtype, op);
     if (algo != RDC_ALGO_AUTO && algo != RDC_ALGO_MESH && algo != RDC_ALGO_DIRECT)
         throw std::invalid_argument("rdc: reduce-scatter has no schedule for algo " + std::to_string(algo) +
                                     " (0 auto, 2 mesh, 6 direct)");
     const size_t esz = rdc_dtype_size(dtype);
-    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
-    if (n_ == 1 || count == 0) return;
-    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    if (!HasWork(buf, count, esz)) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ChannelCall call(ch_.get(), stream);
     const uint64_t nb = (uint64_t)count * esz;
@@ -1316,13 +1337,8 @@ void Communicator::ReduceScatter(void* buf, size_t count, int dtype, int op, hip
         char* b0 = static_cast<char*>(buf);
         if (AllreduceDirect(ks, &b0, &nb, 1, esz, stream, true)) return;
     }
-    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
-    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
-    for (int c = 0; c < n_; ++c) {
-        off[c] = (uint64_t)cb[c] * esz;
-        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
-    }
+    uint64_t off[RDC_MAX_RANKS], len[RDC_MAX_RANKS];
+    SplitBytes(count, esz, n_, off, len);
     LaunchReduceScatter(ks, static_cast<char*>(buf), off, len, nb, esz, stream);
 }
 
@@ -1335,173 +1351,58 @@ void Communicator::ReduceScatter(void* buf, size_t count, int dtype, int op, hip
 // Everything is checked before the first launch; `root` must be the same on
 // every rank (the caller's contract, as for Broadcast).
 void Communicator::ReduceTo(void* buf, size_t count, int dtype, int op, int root, hipStream_t stream) {
-    KernelSet ks;
-    if (!get_kernels(dtype, op, &ks))
-        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
-                                    std::to_string(op) + ")");
-    if (root < 0 || root >= n_)
-        throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " + std::to_string(n_) +
-                                    ")");
+    const KernelSet ks = OpKernels(dtype, op);
+    CheckRoot(root, n_);
     const size_t esz = rdc_dtype_size(dtype);
-    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
-    if (n_ == 1 || count == 0) return;
-    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    if (!HasWork(buf, count, esz)) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ChannelCall call(ch_.get(), stream);
-    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
-    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
-    for (int c = 0; c < n_; ++c) {
-        off[c] = (uint64_t)cb[c] * esz;
-        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
-    }
+    uint64_t off[RDC_MAX_RANKS], len[RDC_MAX_RANKS];
+    SplitBytes(count, esz, n_, off, len);
     LaunchReduceTo(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, root, stream);
 }
 
-// The float32-accumulated Sum of float16 / bfloat16 (include/rdc_amd.h
-// RdcAllreduceAcc32: s = f32(x[c-1]); s = f32(x[c-j]) + s, j = 2..n; one RNE
-// rounding), as the three collectives of the mesh family.  Each runs its
-// sibling's checks in its sibling's order, cuts the same chunks and hands the
-// acc32 KernelSet to the sibling's launcher: same plans, launch kinds, pieces,
-// poison mode and slot reuse.  The pushed mesh is the only schedule.
-namespace {
-KernelSet acc32_kernels(int dtype) {
+// The folds that are no RDC_OP_* operator, as the three collectives of the
+// mesh family.  kAcc32, the float32-accumulated Sum of float16 / bfloat16
+// (include/rdc_amd.h RdcAllreduceAcc32): s = f32(x[c-1]); s = f32(x[c-j]) + s,
+// j = 2..n; one RNE rounding.  kAvg, the mean across ranks (RdcAllreduceAvg):
+// the ring-order Sum fold, in binary32 for float16 / bfloat16, then one IEEE
+// division by n (CollArgs::n) where the owner of a chunk produces the result.
+// Each collective runs its sibling's checks in its sibling's order, cuts the
+// same chunks and hands the fold's KernelSet to the sibling's launcher: same
+// plans, launch kinds, pieces, poison mode and slot reuse.  The pushed mesh is
+// the only schedule.
+KernelSet FoldKernels(MeshFold fold, int dtype) {
     KernelSet ks;
-    if (!get_kernels_acc32(dtype, &ks))
-        throw std::invalid_argument("rdc: float32-accumulated Sum needs float16 or bfloat16, got dtype " +
-                                    std::to_string(dtype));
-    return ks;
+    if (get_kernels_fold(fold, dtype, &ks)) return ks;
+    switch (fold) {
+        case MeshFold::kAcc32:
+            throw std::invalid_argument("rdc: float32-accumulated Sum needs float16 or bfloat16, got dtype " +
+                                        std::to_string(dtype));
+        case MeshFold::kAvg:
+            throw std::invalid_argument("rdc: Avg takes float32, float64, float16 or bfloat16, got dtype " +
+                                        std::to_string(dtype));
+    }
+    throw std::logic_error("rdc: unknown fold");
 }
-}  // namespace
 
-void Communicator::AllreduceAcc32(void* buf, size_t count, int dtype, hipStream_t stream) {
-    const KernelSet ks = acc32_kernels(dtype);
+void Communicator::FoldCollective(MeshColl which, MeshFold fold, void* buf, size_t count, int dtype, int root,
+                                  hipStream_t stream) {
+    const KernelSet ks = FoldKernels(fold, dtype);
+    if (which == MeshColl::kReduceTo) CheckRoot(root, n_);
     const size_t esz = rdc_dtype_size(dtype);
-    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
-    if (n_ == 1 || count == 0) return;
-    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    if (!HasWork(buf, count, esz)) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ChannelCall call(ch_.get(), stream);
-    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
-    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
-    for (int c = 0; c < n_; ++c) {
-        off[c] = (uint64_t)cb[c] * esz;
-        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
+    uint64_t off[RDC_MAX_RANKS], len[RDC_MAX_RANKS];
+    SplitBytes(count, esz, n_, off, len);
+    char* b = static_cast<char*>(buf);
+    const uint64_t total = (uint64_t)count * esz;
+    switch (which) {
+        case MeshColl::kAllreduce: LaunchRanges(ks, b, off, len, total, esz, RDC_ALGO_MESH, stream); break;
+        case MeshColl::kReduceScatter: LaunchReduceScatter(ks, b, off, len, total, esz, stream); break;
+        case MeshColl::kReduceTo: LaunchReduceTo(ks, b, off, len, total, esz, root, stream); break;
     }
-    LaunchRanges(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, RDC_ALGO_MESH, stream);
-}
-
-void Communicator::ReduceScatterAcc32(void* buf, size_t count, int dtype, hipStream_t stream) {
-    const KernelSet ks = acc32_kernels(dtype);
-    const size_t esz = rdc_dtype_size(dtype);
-    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
-    if (n_ == 1 || count == 0) return;
-    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    ChannelCall call(ch_.get(), stream);
-    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
-    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
-    for (int c = 0; c < n_; ++c) {
-        off[c] = (uint64_t)cb[c] * esz;
-        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
-    }
-    LaunchReduceScatter(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, stream);
-}
-
-void Communicator::ReduceToAcc32(void* buf, size_t count, int dtype, int root, hipStream_t stream) {
-    const KernelSet ks = acc32_kernels(dtype);
-    if (root < 0 || root >= n_)
-        throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " + std::to_string(n_) +
-                                    ")");
-    const size_t esz = rdc_dtype_size(dtype);
-    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
-    if (n_ == 1 || count == 0) return;
-    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    ChannelCall call(ch_.get(), stream);
-    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
-    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
-    for (int c = 0; c < n_; ++c) {
-        off[c] = (uint64_t)cb[c] * esz;
-        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
-    }
-    LaunchReduceTo(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, root, stream);
-}
-
-// Avg, the mean across ranks (include/rdc_amd.h RdcAllreduceAvg: the ring-order
-// Sum fold, in binary32 for float16 / bfloat16, then one IEEE division by n
-// where the owner of a chunk produces the result), as the three collectives of
-// the mesh family.  Built like the float32-accumulated Sum above: the
-// siblings' checks in their order, the same chunks, the avg KernelSet handed
-// to the siblings' launchers.  The divisor is CollArgs::n; nothing else is new.
-namespace {
-KernelSet avg_kernels(int dtype) {
-    KernelSet ks;
-    if (!get_kernels_avg(dtype, &ks))
-        throw std::invalid_argument("rdc: Avg takes float32, float64, float16 or bfloat16, got dtype " +
-                                    std::to_string(dtype));
-    return ks;
-}
-}  // namespace
-
-void Communicator::AllreduceAvg(void* buf, size_t count, int dtype, hipStream_t stream) {
-    const KernelSet ks = avg_kernels(dtype);
-    const size_t esz = rdc_dtype_size(dtype);
-    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
-    if (n_ == 1 || count == 0) return;
-    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    ChannelCall call(ch_.get(), stream);
-    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
-    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
-    for (int c = 0; c < n_; ++c) {
-        off[c] = (uint64_t)cb[c] * esz;
-        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
-    }
-    LaunchRanges(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, RDC_ALGO_MESH, stream);
-}
-
-void Communicator::ReduceScatterAvg(void* buf, size_t count, int dtype, hipStream_t stream) {
-    const KernelSet ks = avg_kernels(dtype);
-    const size_t esz = rdc_dtype_size(dtype);
-    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
-    if (n_ == 1 || count == 0) return;
-    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    ChannelCall call(ch_.get(), stream);
-    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
-    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
-    for (int c = 0; c < n_; ++c) {
-        off[c] = (uint64_t)cb[c] * esz;
-        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
-    }
-    LaunchReduceScatter(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, stream);
-}
-
-void Communicator::ReduceToAvg(void* buf, size_t count, int dtype, int root, hipStream_t stream) {
-    const KernelSet ks = avg_kernels(dtype);
-    if (root < 0 || root >= n_)
-        throw std::invalid_argument("rdc: reduce root " + std::to_string(root) + " outside [0, " + std::to_string(n_) +
-                                    ")");
-    const size_t esz = rdc_dtype_size(dtype);
-    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
-    if (n_ == 1 || count == 0) return;
-    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    ChannelCall call(ch_.get(), stream);
-    int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-    SplitRanges((int64_t)count, n_, cb, ce);  // utils::Split (include/utils/utils.h:59-70)
-    uint64_t off[RDC_MAX_RANKS] = {0}, len[RDC_MAX_RANKS] = {0};
-    for (int c = 0; c < n_; ++c) {
-        off[c] = (uint64_t)cb[c] * esz;
-        len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
-    }
-    LaunchReduceTo(ks, static_cast<char*>(buf), off, len, (uint64_t)count * esz, esz, root, stream);
 }
 
 // The prefix reduction across ranks (MPI_Scan / MPI_Exscan), in place: rank r
@@ -1512,16 +1413,11 @@ void Communicator::ReduceToAvg(void* buf, size_t count, int dtype, int root, hip
 // has no scan, so no tree branch applies).  Everything is checked before the
 // first launch.
 void Communicator::Scan(void* buf, size_t count, int dtype, int op, int exclusive, hipStream_t stream) {
-    KernelSet ks;
-    if (!get_kernels(dtype, op, &ks))
-        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
-                                    std::to_string(op) + ")");
+    const KernelSet ks = OpKernels(dtype, op);
     if (exclusive != 0 && exclusive != 1)
         throw std::invalid_argument("rdc: scan exclusive " + std::to_string(exclusive) + " outside {0, 1}");
     const size_t esz = rdc_dtype_size(dtype);
-    if ((uintptr_t)buf % esz) throw std::invalid_argument("rdc: buffer not aligned to its element size");
-    if (n_ == 1 || count == 0) return;
-    if (buf == nullptr) throw std::invalid_argument("rdc: null buffer");
+    if (!HasWork(buf, count, esz)) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ChannelCall call(ch_.get(), stream);
     LaunchScan(ks, static_cast<char*>(buf), (uint64_t)count, esz, exclusive, stream);
@@ -2134,12 +2030,9 @@ bool Communicator::AllreduceDirect(const KernelSet& ks, char* const* bufs, const
     tile = (tile + 255) & ~(uint64_t)255;
     int grid = 1;
     if (nbuf == 1) {
-        int64_t cb[RDC_MAX_RANKS], ce[RDC_MAX_RANKS];
-        SplitRanges((int64_t)(bytes[0] / esz), n_, cb, ce);
+        SplitBytes(bytes[0] / esz, esz, n_, a.off, a.len);
         a.user = bufs[0];
         for (int c = 0; c < n_; ++c) {
-            a.off[c] = (uint64_t)cb[c] * esz;
-            a.len[c] = (uint64_t)(ce[c] - cb[c]) * esz;
             a.cbuf[c] = amap[(size_t)c * kDirectAllocsMax + slots[c].buf[0].alloc] + slots[c].buf[0].off;
         }
         const int tiles = (int)std::max<uint64_t>(1, (a.len[rank_] + tile - 1) / tile);
@@ -2281,10 +2174,7 @@ void Communicator::DirectUnmapAll() {
 
 void Communicator::AllreduceRanges(void* buf, const uint64_t* off, const uint64_t* len, int dtype, int op,
                                    hipStream_t stream, const int8_t* fold) {
-    KernelSet ks;
-    if (!get_kernels(dtype, op, &ks))
-        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
-                                    std::to_string(op) + ")");
+    const KernelSet ks = OpKernels(dtype, op);
     if (n_ == 1) return;
     const size_t esz = rdc_dtype_size(dtype);
     uint64_t total = 0, sum = 0, first = ~0ull;
@@ -2659,10 +2549,7 @@ const Communicator::PackEntry& Communicator::PackTable(void* const* bufs, const 
 
 void Communicator::AllreduceCoalesced(void* const* bufs, const size_t* counts, int nbuf, int dtype, int op,
                                       hipStream_t stream, int algo) {
-    KernelSet ks;
-    if (!get_kernels(dtype, op, &ks))
-        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
-                                    std::to_string(op) + ")");
+    const KernelSet ks = OpKernels(dtype, op);
     if (nbuf < 0 || (nbuf > 0 && (!bufs || !counts))) throw std::invalid_argument("rdc: bad buffer list");
     const size_t esz = rdc_dtype_size(dtype);
     int misaligned = 0;
@@ -3236,10 +3123,7 @@ bool Communicator::SmallHostAllreduce(void* host, size_t count, int dtype, int o
     if (n_ == 1 || bytes == 0 || bytes > RDC_SVC_MAX_BYTES || !ch_ || !ch_->svc_region || !ch_->svc_enabled ||
         share_max_ > SmallService::ShareMax())
         return false;
-    KernelSet ks;
-    if (!get_kernels(dtype, op, &ks))
-        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
-                                    std::to_string(op) + ")");
+    const KernelSet ks = OpKernels(dtype, op);
     SmallService* svc;
     {
         std::lock_guard<std::mutex> lk(ch_->mu);
@@ -3429,10 +3313,7 @@ void Communicator::RaiseIfError(uint32_t e) const {
 }
 
 void DeviceReduce(void* dst, const void* src, size_t count, int dtype, int op, hipStream_t stream, int grid) {
-    KernelSet ks;
-    if (!get_kernels(dtype, op, &ks))
-        throw std::invalid_argument("rdc: unsupported (dtype, op) = (" + std::to_string(dtype) + ", " +
-                                    std::to_string(op) + ")");
+    const KernelSet ks = OpKernels(dtype, op);
     const size_t esz = rdc_dtype_size(dtype);
     if ((uintptr_t)dst % esz || (uintptr_t)src % esz)
         throw std::invalid_argument("rdc: buffer not aligned to its element size");

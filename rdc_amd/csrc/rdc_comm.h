@@ -22,6 +22,7 @@
 
 #include "rdc_bootstrap.h"
 #include "rdc_common.h"
+#include "rdc_kernels.h"
 #include "rdc_plan.h"
 
 #include "rdc_vmem.h"
@@ -56,7 +57,6 @@ struct CommConfig {
     int poison = 0;
 };
 
-struct KernelSet;
 struct P2PCtl;
 class P2PEngine;
 class WorkComp;
@@ -213,6 +213,17 @@ struct DirectDesc {
     DirectBuf buf[kDirectBufsMax];
 };
 
+// byte offset and length of every chunk of utils::Split(0, count, n)
+// (include/utils/utils.h:59-70) over elements of esz bytes; entries n ..
+// RDC_MAX_RANKS - 1 are zero
+void SplitBytes(size_t count, size_t esz, int n, uint64_t* off, uint64_t* len);
+// a rooted collective's root outside [0, n): std::invalid_argument
+void CheckRoot(int root, int n);
+// the collectives of the mesh family, and a fold's kernels for them
+// (get_kernels_fold); a dtype the fold does not take: std::invalid_argument
+enum class MeshColl { kAllreduce, kReduceScatter, kReduceTo };
+KernelSet FoldKernels(MeshFold fold, int dtype);
+
 class Communicator {
 public:
     // Multi-process: one communicator per process, peers found through `bs`
@@ -243,26 +254,21 @@ public:
     // unsupported (dtype, op), a misaligned or null buffer.  root must be the
     // same on every rank.  n == 1 or count == 0: nothing is launched.
     void ReduceTo(void* buf, size_t count, int dtype, int op, int root, hipStream_t stream);
-    // The float32-accumulated Sum of float16 / bfloat16 buffers (dtype 10 / 11;
-    // the rule: include/rdc_amd.h RdcAllreduceAcc32) as allreduce,
-    // reduce-scatter and rooted reduce: their siblings' checks, chunk map,
-    // launches and untouched bytes, on the pushed mesh at every size and every
-    // n (no one-shot, ring, tree, pull or direct schedule; cfg_.ring_mincount
-    // is not consulted).  Any other dtype is refused before any launch.
-    void AllreduceAcc32(void* buf, size_t count, int dtype, hipStream_t stream);
-    void ReduceScatterAcc32(void* buf, size_t count, int dtype, hipStream_t stream);
-    void ReduceToAcc32(void* buf, size_t count, int dtype, int root, hipStream_t stream);
-    // Avg, the mean across ranks of float32 / float64 / float16 / bfloat16
-    // buffers (dtype 6 / 7 / 10 / 11; the rule: include/rdc_amd.h
-    // RdcAllreduceAvg: the ring-order Sum fold — in binary32 for the 16-bit
-    // types — then one IEEE division by n before the single store) as
-    // allreduce, reduce-scatter and rooted reduce: their siblings' checks,
-    // chunk map, launches and untouched bytes, on the pushed mesh at every
-    // size and every n (cfg_.ring_mincount is not consulted).  Any other dtype
-    // is refused before any launch.
-    void AllreduceAvg(void* buf, size_t count, int dtype, hipStream_t stream);
-    void ReduceScatterAvg(void* buf, size_t count, int dtype, hipStream_t stream);
-    void ReduceToAvg(void* buf, size_t count, int dtype, int root, hipStream_t stream);
+    // The folds that are no RDC_OP_* operator, as allreduce, reduce-scatter
+    // and rooted reduce (`root`: kReduceTo only):
+    //   MeshFold::kAcc32  the float32-accumulated Sum of float16 / bfloat16
+    //                     buffers (dtype 10 / 11; include/rdc_amd.h RdcAllreduceAcc32)
+    //   MeshFold::kAvg    the mean across ranks of float32 / float64 / float16 /
+    //                     bfloat16 buffers (dtype 6 / 7 / 10 / 11; include/rdc_amd.h
+    //                     RdcAllreduceAvg: the ring-order Sum fold, in binary32
+    //                     for the 16-bit types, then one IEEE division by n
+    //                     before the single store)
+    // Each has its sibling's checks, chunk map, launches and untouched bytes,
+    // on the pushed mesh at every size and every n (no one-shot, ring, tree,
+    // pull or direct schedule; cfg_.ring_mincount is not consulted).  A dtype
+    // the fold does not take is refused before any launch.
+    void FoldCollective(MeshColl which, MeshFold fold, void* buf, size_t count, int dtype, int root,
+                        hipStream_t stream);
     // In-place prefix reduction across ranks (MPI_Scan; exclusive = 1:
     // MPI_Exscan), stream-ordered: rank r ends with y[r] (exclusive: r > 0 with
     // y[r-1]), y[0] = x[0], y[q] = OP::Reduce(dst = y[q-1], src = x[q]); rank
@@ -451,6 +457,8 @@ private:
     void Attach(const std::shared_ptr<Channel>& ch);     // one more user of the channel, then Alias()
     void Alias();                                        // copy the channel's pointers into the names below
     void FillArgsCommon(CollArgs* a) const;
+    // false: nothing to launch (world size 1 or count 0); refuses a misaligned or a null buffer
+    bool HasWork(const void* buf, size_t count, size_t esz) const;
     int PickAlgo(int algo) const;
     int PickAlgo(int algo, uint64_t bytes) const;
     // units != null: coalesced mesh over a device PackUnit table (off/len = packed chunk ranges)

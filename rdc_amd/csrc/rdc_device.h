@@ -302,7 +302,7 @@ __device__ __forceinline__ v4u reduce16<RDC_OP_SUM, bf16_t>(v4u d, v4u s) {
 // kOpSumAcc32 is a template tag for the mesh family's fold (mesh_fold_elem /
 // mesh_reduce_range, rdc_kernels_impl.h), not an RDC_OP_* code: no OpF and no
 // reduce16 exist for it, get_kernels never sees it, and only
-// rdc_kernels_acc32.hip instantiates kernels with it.  The owner of a chunk
+// rdc_kernels_fold.hip instantiates kernels with it.  The owner of a chunk
 // holds all n raw 16-bit contributions before it folds, so it widens each to
 // binary32, adds them in the ring order and rounds ONCE (RNE).
 constexpr int kOpSumAcc32 = 0x100;
@@ -345,7 +345,7 @@ template <> __device__ __forceinline__ uint32_t narrow2<bf16_t>(f2 s) {
 
 // ---- Avg: the mean across ranks (the rule: include/rdc_amd.h, RdcAllreduceAvg) ----
 // kOpAvg is a template tag like kOpSumAcc32, not an RDC_OP_* code: get_kernels
-// never sees it and only rdc_kernels_avg.hip instantiates kernels with it.
+// never sees it and only rdc_kernels_fold.hip instantiates kernels with it.
 // The owner of a chunk is the only place a result is produced, so it divides
 // there, before the single store.  float / double: the ordinary Sum's ring
 // fold in T, then one IEEE division by T(n).  float16 / bfloat16: the acc32
@@ -355,7 +355,7 @@ template <> __device__ __forceinline__ uint32_t narrow2<bf16_t>(f2 s) {
 constexpr int kOpAvg = 0x101;
 // the folds that accumulate 16-bit elements in binary32
 template <int OP, typename T>
-constexpr bool kFoldAcc32 = OP == kOpSumAcc32 || (OP == kOpAvg && sizeof(T) == 2);
+constexpr bool kAccumulateF32 = OP == kOpSumAcc32 || (OP == kOpAvg && sizeof(T) == 2);
 namespace avg {
 // the lanes of a 16-byte vector of float (4) / double (2), each divided by T(n)
 template <typename T>

@@ -30,14 +30,14 @@ struct KernelSet {
 
 // false if (dtype, op) is not a valid reference combination
 bool get_kernels(int dtype, int op, KernelSet* ks);
-// the float32-accumulated Sum of float16 / bfloat16 (rdc_kernels_acc32.hip):
+// The folds of the mesh family that are no RDC_OP_* operator
+// (rdc_kernels_fold.hip): kAcc32, the float32-accumulated Sum of float16 /
+// bfloat16; kAvg, the mean across ranks of float32 / float64 / float16 /
+// bfloat16.
+enum class MeshFold { kAcc32, kAvg };
 // fills mesh, rscatter, rooted and occupancy, every other member is null;
-// false for any other dtype
-bool get_kernels_acc32(int dtype, KernelSet* ks);
-// Avg, the mean across ranks of float32 / float64 / float16 / bfloat16
-// (rdc_kernels_avg.hip): fills mesh, rscatter, rooted and occupancy, every
-// other member is null; false for any other dtype
-bool get_kernels_avg(int dtype, KernelSet* ks);
+// false for a dtype the fold does not take
+bool get_kernels_fold(MeshFold fold, int dtype, KernelSet* ks);
 // resident blocks per CU of k_bcast / k_allgather / k_alltoall
 int occupancy_bcast();
 int occupancy_allgather();

@@ -192,7 +192,7 @@ __device__ __forceinline__ void mesh_fold_elem(const CollArgs& a, char* own, con
         return q == r ? *reinterpret_cast<const T*>(own + e) : ld_elem_sys<T>(slot0 + q * a.slot_bytes + e);
     };
     T acc;
-    if constexpr (kFoldAcc32<OP, T>) {  // binary32 accumulator, one rounding (rdc_device.h acc32)
+    if constexpr (kAccumulateF32<OP, T>) {  // binary32 accumulator, one rounding (rdc_device.h acc32)
         float s = acc32::widen<T>(val((f - 1 + n) % n));
         for (int k = 2; k <= n; ++k) s = acc32::widen<T>(val((f - k + n) % n)) + s;
         if constexpr (OP == kOpAvg) s = s / (float)n;  // the mean, before the one rounding
@@ -278,7 +278,7 @@ __device__ __forceinline__ void mesh_reduce_range(const CollArgs& a, char* own, 
         for (int u = 0; u < U; ++u) {
             if (!live[u]) continue;
             v4u acc;
-            if constexpr (kFoldAcc32<OP, T>) {
+            if constexpr (kAccumulateF32<OP, T>) {
                 // eight binary32 accumulators per vector, the k order of the
                 // ring, one conversion back (rdc_device.h acc32)
                 acc32::f2 s[4];
@@ -2132,8 +2132,72 @@ inline unsigned debug_lds_pad() {
     return pad;
 }
 
+// One collective kernel on the host side, given its NMAX = 8 and NMAX = 16
+// instantiations (a kernel without a width: itself, once).  launch picks the
+// width from a.n; occupancy(n) is the resident blocks per CU of the width n
+// ranks use, queried once per width.  Every launch and every query reserves
+// debug_lds_pad() bytes of dynamic LDS.
+using CollKernel = void (*)(CollArgs);
+
+template <CollKernel K8, CollKernel K16 = K8>
+struct Launcher {
+    static hipError_t launch(const CollArgs& a, int grid, hipStream_t s) {
+        if (a.n <= 8)
+            hipLaunchKernelGGL(K8, dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
+        else
+            hipLaunchKernelGGL(K16, dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
+        return hipGetLastError();
+    }
+    static int occupancy(int n) {
+        static int cache[2] = {0, 0};  // [NMAX 8, NMAX 16]; 0 = not queried yet
+        int& c = cache[n > 8 ? 1 : 0];
+        if (c > 0) return c;
+        int b = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, n > 8 ? K16 : K8, kBlock, debug_lds_pad()) != hipSuccess ||
+            b <= 0) {
+            (void)hipGetLastError();
+            b = 1;  // unknown: one block per CU is always resident
+        }
+        return c = b;
+    }
+};
+
+// The mesh family (k_mesh, k_rscatter, k_rooted) under one (OP, T): all that
+// a fold tag (kOpSumAcc32, kOpAvg; rdc_kernels_fold.hip) instantiates.
+template <int OP, typename T>
+struct MeshFamilyKernels {
+    using Mesh = Launcher<k_mesh<OP, T, 8>, k_mesh<OP, T, 16>>;
+    using RScatter = Launcher<k_rscatter<OP, T, 8>, k_rscatter<OP, T, 16>>;
+    using Rooted = Launcher<k_rooted<OP, T, 8>, k_rooted<OP, T, 16>>;
+
+    static int occupancy(int kind, int n) {
+        switch (kind) {
+            case RDC_KIND_RSCATTER: return RScatter::occupancy(n);
+            case RDC_KIND_ROOTED: return Rooted::occupancy(n);
+            default: return Mesh::occupancy(n);
+        }
+    }
+    static bool fill(KernelSet* ks) {
+        *ks = KernelSet();  // every other member null: never called on a fold's path
+        ks->mesh = &Mesh::launch;
+        ks->rscatter = &RScatter::launch;
+        ks->rooted = &Rooted::launch;
+        ks->occupancy = &occupancy;
+        return true;
+    }
+};
+
+// Every kernel of an RDC_OP_* operator.
 template <int OP, typename T>
 struct Kernels {
+    using Family = MeshFamilyKernels<OP, T>;
+    using Oneshot = Launcher<k_oneshot<OP, T, 8>, k_oneshot<OP, T, 16>>;
+    using Tree = Launcher<k_tree<OP, T, 8>, k_tree<OP, T, 16>>;
+    using Direct = Launcher<k_direct<OP, T, 8>, k_direct<OP, T, 16>>;
+    using RScatterDirect = Launcher<k_rscatter_direct<OP, T, 8>, k_rscatter_direct<OP, T, 16>>;
+    using Ring = Launcher<k_ring<OP, T>>;
+    using Scan = Launcher<k_scan<OP, T>>;
+
     static hipError_t reduce(char* dst, const char* src, uint64_t nbytes, int grid, hipStream_t s) {
         if ((((uintptr_t)dst ^ (uintptr_t)src) & 15) == 0) {
             hipLaunchKernelGGL((k_reduce<OP, T, 2>), dim3(grid), dim3(kBlock), 0, s, dst, src, nbytes);
@@ -2141,56 +2205,6 @@ struct Kernels {
             hipLaunchKernelGGL((k_reduce_unaligned<OP, T>), dim3(grid), dim3(kBlock), 0, s, dst, src,
                                nbytes / sizeof(T));
         }
-        return hipGetLastError();
-    }
-    static hipError_t mesh(const CollArgs& a, int grid, hipStream_t s) {
-        if (a.n <= 8)
-            hipLaunchKernelGGL((k_mesh<OP, T, 8>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        else
-            hipLaunchKernelGGL((k_mesh<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        return hipGetLastError();
-    }
-    static hipError_t oneshot(const CollArgs& a, int grid, hipStream_t s) {
-        if (a.n <= 8)
-            hipLaunchKernelGGL((k_oneshot<OP, T, 8>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        else
-            hipLaunchKernelGGL((k_oneshot<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        return hipGetLastError();
-    }
-    static hipError_t direct(const CollArgs& a, int grid, hipStream_t s) {
-        if (a.n <= 8)
-            hipLaunchKernelGGL((k_direct<OP, T, 8>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        else
-            hipLaunchKernelGGL((k_direct<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        return hipGetLastError();
-    }
-    static hipError_t rscatter(const CollArgs& a, int grid, hipStream_t s) {
-        if (a.n <= 8)
-            hipLaunchKernelGGL((k_rscatter<OP, T, 8>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        else
-            hipLaunchKernelGGL((k_rscatter<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        return hipGetLastError();
-    }
-    static hipError_t rscatter_direct(const CollArgs& a, int grid, hipStream_t s) {
-        if (a.n <= 8)
-            hipLaunchKernelGGL((k_rscatter_direct<OP, T, 8>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        else
-            hipLaunchKernelGGL((k_rscatter_direct<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        return hipGetLastError();
-    }
-    static hipError_t rooted(const CollArgs& a, int grid, hipStream_t s) {
-        if (a.n <= 8)
-            hipLaunchKernelGGL((k_rooted<OP, T, 8>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        else
-            hipLaunchKernelGGL((k_rooted<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        return hipGetLastError();
-    }
-    static hipError_t ring(const CollArgs& a, int grid, hipStream_t s) {
-        hipLaunchKernelGGL((k_ring<OP, T>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        return hipGetLastError();
-    }
-    static hipError_t scan(const CollArgs& a, int grid, hipStream_t s) {
-        hipLaunchKernelGGL((k_scan<OP, T>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
         return hipGetLastError();
     }
     static hipError_t svc(const SvcArgs& a, hipStream_t s) {
@@ -2205,84 +2219,42 @@ struct Kernels {
             hipLaunchKernelGGL((k_svc<OP, T, 16, 256, false>), dim3(1), dim3(256), 0, s, a);
         return hipGetLastError();
     }
-    static hipError_t tree(const CollArgs& a, int grid, hipStream_t s) {
-        if (a.n <= 8)
-            hipLaunchKernelGGL((k_tree<OP, T, 8>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        else
-            hipLaunchKernelGGL((k_tree<OP, T, 16>), dim3(grid), dim3(kBlock), debug_lds_pad(), s, a);
-        return hipGetLastError();
-    }
     static int occupancy(int kind, int n) {
-        // [mesh 8, mesh 16, oneshot 8, oneshot 16, ring, tree 8, tree 16, direct 8, direct 16,
-        //  rscatter 8, rscatter 16, rscatter direct 8, rscatter direct 16, rooted 8, rooted 16, scan];
-        // 0 = not queried yet
-        static int cache[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        const int wide = n > 8 ? 1 : 0;
-        const int slot = kind == RDC_KIND_RING      ? 4
-                         : kind == RDC_KIND_TREE    ? 5 + wide
-                         : kind == RDC_KIND_ONESHOT ? 2 + wide
-                         : kind == RDC_KIND_DIRECT  ? 7 + wide
-                         : kind == RDC_KIND_RSCATTER ? 9 + wide
-                         : kind == RDC_KIND_RSCATTER_DIRECT ? 11 + wide
-                         : kind == RDC_KIND_ROOTED  ? 13 + wide
-                         : kind == RDC_KIND_SCAN    ? 15
-                                                    : wide;
-        if (cache[slot] > 0) return cache[slot];
-        int b = 0;
-        hipError_t e = hipSuccess;
-        switch (slot) {
-            case 0: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_mesh<OP, T, 8>, kBlock, debug_lds_pad()); break;
-            case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_mesh<OP, T, 16>, kBlock, debug_lds_pad()); break;
-            case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_oneshot<OP, T, 8>, kBlock, debug_lds_pad()); break;
-            case 3: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_oneshot<OP, T, 16>, kBlock, debug_lds_pad()); break;
-            case 5: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_tree<OP, T, 8>, kBlock, debug_lds_pad()); break;
-            case 6: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_tree<OP, T, 16>, kBlock, debug_lds_pad()); break;
-            case 7: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_direct<OP, T, 8>, kBlock, debug_lds_pad()); break;
-            case 8: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_direct<OP, T, 16>, kBlock, debug_lds_pad()); break;
-            case 9: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter<OP, T, 8>, kBlock, debug_lds_pad()); break;
-            case 10: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter<OP, T, 16>, kBlock, debug_lds_pad()); break;
-            case 11: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter_direct<OP, T, 8>, kBlock, debug_lds_pad()); break;
-            case 12: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rscatter_direct<OP, T, 16>, kBlock, debug_lds_pad()); break;
-            case 13: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rooted<OP, T, 8>, kBlock, debug_lds_pad()); break;
-            case 14: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rooted<OP, T, 16>, kBlock, debug_lds_pad()); break;
-            case 15: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_scan<OP, T>, kBlock, debug_lds_pad()); break;
-            default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_ring<OP, T>, kBlock, debug_lds_pad()); break;
+        switch (kind) {
+            case RDC_KIND_RING: return Ring::occupancy(n);
+            case RDC_KIND_TREE: return Tree::occupancy(n);
+            case RDC_KIND_ONESHOT: return Oneshot::occupancy(n);
+            case RDC_KIND_DIRECT: return Direct::occupancy(n);
+            case RDC_KIND_RSCATTER_DIRECT: return RScatterDirect::occupancy(n);
+            case RDC_KIND_SCAN: return Scan::occupancy(n);
+            default: return Family::occupancy(kind, n);
         }
-        if (e != hipSuccess || b <= 0) {
-            (void)hipGetLastError();
-            b = 1;  // unknown: one block per CU is always resident
-        }
-        cache[slot] = b;
-        return b;
+    }
+    static bool fill(KernelSet* ks) {
+        Family::fill(ks);
+        ks->reduce = &reduce;
+        ks->ring = &Ring::launch;
+        ks->oneshot = &Oneshot::launch;
+        ks->tree = &Tree::launch;
+        ks->direct = &Direct::launch;
+        ks->rscatter_direct = &RScatterDirect::launch;
+        ks->scan = &Scan::launch;
+        ks->svc = &svc;
+        ks->occupancy = &occupancy;
+        return true;
     }
 };
-
-
-#define RDC_SET(T)                        \
-    ks->reduce = &Kernels<OP, T>::reduce; \
-    ks->mesh = &Kernels<OP, T>::mesh;     \
-    ks->ring = &Kernels<OP, T>::ring;     \
-    ks->direct = &Kernels<OP, T>::direct; \
-    ks->rscatter = &Kernels<OP, T>::rscatter; \
-    ks->rscatter_direct = &Kernels<OP, T>::rscatter_direct; \
-    ks->rooted = &Kernels<OP, T>::rooted; \
-    ks->scan = &Kernels<OP, T>::scan;     \
-    ks->oneshot = &Kernels<OP, T>::oneshot; \
-    ks->tree = &Kernels<OP, T>::tree;       \
-    ks->svc = &Kernels<OP, T>::svc;         \
-    ks->occupancy = &Kernels<OP, T>::occupancy; \
-    return true;
 
 // integer element types (every operator)
 template <int OP>
 inline bool pick_int(int dtype, KernelSet* ks) {
     switch (dtype) {
-        case RDC_DT_INT8: RDC_SET(int8_t)
-        case RDC_DT_UINT8: RDC_SET(uint8_t)
-        case RDC_DT_INT32: RDC_SET(int32_t)
-        case RDC_DT_UINT32: RDC_SET(uint32_t)
-        case RDC_DT_INT64: case RDC_DT_LONGLONG: RDC_SET(int64_t)
-        case RDC_DT_UINT64: case RDC_DT_ULONGLONG: RDC_SET(uint64_t)
+        case RDC_DT_INT8: return Kernels<OP, int8_t>::fill(ks);
+        case RDC_DT_UINT8: return Kernels<OP, uint8_t>::fill(ks);
+        case RDC_DT_INT32: return Kernels<OP, int32_t>::fill(ks);
+        case RDC_DT_UINT32: return Kernels<OP, uint32_t>::fill(ks);
+        case RDC_DT_INT64: case RDC_DT_LONGLONG: return Kernels<OP, int64_t>::fill(ks);
+        case RDC_DT_UINT64: case RDC_DT_ULONGLONG: return Kernels<OP, uint64_t>::fill(ks);
         default: return false;
     }
 }
@@ -2292,10 +2264,10 @@ template <int OP>
 inline bool pick_arith(int dtype, KernelSet* ks) {
     if (pick_int<OP>(dtype, ks)) return true;
     switch (dtype) {
-        case RDC_DT_FLOAT32: RDC_SET(float)
-        case RDC_DT_FLOAT64: RDC_SET(double)
-        case RDC_DT_FLOAT16: RDC_SET(_Float16)
-        case RDC_DT_BFLOAT16: RDC_SET(bf16_t)
+        case RDC_DT_FLOAT32: return Kernels<OP, float>::fill(ks);
+        case RDC_DT_FLOAT64: return Kernels<OP, double>::fill(ks);
+        case RDC_DT_FLOAT16: return Kernels<OP, _Float16>::fill(ks);
+        case RDC_DT_BFLOAT16: return Kernels<OP, bf16_t>::fill(ks);
         default: return false;
     }
 }
@@ -2304,8 +2276,8 @@ inline bool pick_arith(int dtype, KernelSet* ks) {
 template <int OP>
 inline bool pick_loc(int dtype, KernelSet* ks) {
     switch (dtype) {
-        case RDC_DT_F32_I32: RDC_SET(pair_f32_t)
-        case RDC_DT_I32_I32: RDC_SET(pair_i32_t)
+        case RDC_DT_F32_I32: return Kernels<OP, pair_f32_t>::fill(ks);
+        case RDC_DT_I32_I32: return Kernels<OP, pair_i32_t>::fill(ks);
         default: return false;
     }
 }
@@ -2315,11 +2287,10 @@ inline bool pick_loc(int dtype, KernelSet* ks) {
 template <int OP>
 inline bool pick_loc16(int dtype, KernelSet* ks) {
     switch (dtype) {
-        case RDC_DT_F64_I64: RDC_SET(pair_f64_t)
-        case RDC_DT_I64_I64: RDC_SET(pair_i64_t)
+        case RDC_DT_F64_I64: return Kernels<OP, pair_f64_t>::fill(ks);
+        case RDC_DT_I64_I64: return Kernels<OP, pair_i64_t>::fill(ks);
         default: return false;
     }
 }
-#undef RDC_SET
 
 }  // namespace rdc_amd
